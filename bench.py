@@ -1,7 +1,10 @@
 """bench.py -- training imgs/s of the CSBSR joint SR+segmentation hot path on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--lr-size 448] [--micro-batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--lr-size 448] [--micro-batch 8] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...          (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the legs that are not the headline: the
+per-launch event leg (roofline block, --dump-layers), the H2D leg, the other detector precision mode and the CPU baseline.
 
 `python bench.py --gpus N` with N > 1 and no launcher on the command line starts the N ranks itself (a `torch.distributed.run` CHILD
 process, before this process touches the GPU -- one command drives all GPUs like the reference's train.py:105-112) and relays rank 0's
@@ -90,6 +93,24 @@ def cpu_baseline(lr=64, seconds_budget=24.0, threads=0, min_steps=3):
                       f"divided by (448/{lr})^2 = {scale:.2f} (conv work linear in pixels) to quote it at LR 448"}
 
 
+DUMP_SAMPLE = 1 << 22       # elements kept of a larger tensor: three such samples (SR, segmentation, parameters) = 48 MB of float32
+
+
+def dump_outputs(tensors, out_dir):
+    """Write each tensor as out_dir/<name>.npy in float32: whole when it has at most DUMP_SAMPLE elements, else the elements at
+    DUMP_SAMPLE flat indices drawn from a generator seeded by the name (the same positions in every run of the same shape), sorted."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tensors.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -120,8 +141,16 @@ def main():
     ap.add_argument("--watchdog-s", type=int, default=int(os.environ.get("CSBSR_BENCH_WATCHDOG", "0")),
                     help="dump every thread's Python stack to stderr and exit if the run is still going after this many seconds (0 = off): a hung "
                          "collective in a multi-rank run then says where each rank stands instead of timing out silently")
-    ap.add_argument("--dump-layers", default=None, help="write the per-launch conv / wgrad log of the timed region (layer, shape, kernel, ms) as JSON")
+    ap.add_argument("--dump-layers", default=None, help="write the per-launch conv / wgrad log of the timed region (layer, shape, kernel, ms) as JSON (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (event leg + roofline, H2D leg, other precision leg, CPU baseline; each can "
+                         "still be turned off with its --no-* option); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (losses, SR / segmentation / kernel predictions, the stepped fp32 "
+                         "parameters) as DIR/<name>.npy in float32; tensors above 2^22 elements as a fixed seeded sample (rank 0)")
     args = ap.parse_args()
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers needs --full (the per-launch log comes from the event leg)")
 
     launched = "WORLD_SIZE" in os.environ
     if args.gpus < 1:
@@ -214,8 +243,9 @@ def main():
     beta = cfg.SOLVER.TASK_LOSS_WEIGHT
 
     host = None
+    outputs = {}
 
-    def step():
+    def step(keep=False):
         opt.zero_grad(set_to_none=True)
         if host is not None:        # H2D leg only: the batch crosses PCIe inside the step, as the reference's loader hands it over
             xx, hh, mm, kk = (t.to(dev, non_blocking=True) for t in host)
@@ -225,6 +255,8 @@ def main():
         loss = (1 - beta) * sr_l.mean() + beta * seg_l.mean()          # trainer.py:406-438, iter >= 30001
         loss.backward()
         opt.step()
+        if keep:        # --dump-outputs: the last timed step's results (references only; copied out after the timed region)
+            outputs.update(loss=loss.detach(), segment_loss=seg_l.detach(), sr_loss=sr_l.detach(), segment_preds=seg, sr_preds=sr, kernel_preds=kp)
         return float(loss.detach())
 
     for _ in range(args.warmup):
@@ -238,7 +270,7 @@ def main():
     last = 0.0
     ovf0, bad_loss = model.overflow_steps, []
     for i_ in range(args.steps):
-        last = step()
+        last = step(keep=args.dump_outputs is not None and i_ == args.steps - 1)
         if not math.isfinite(last):
             bad_loss.append((i_, last))
     torch.cuda.synchronize()
@@ -258,11 +290,16 @@ def main():
     ms = dt / args.steps * 1e3
     imgs = B * world * args.steps / dt
     peak_main = torch.cuda.max_memory_allocated(dev)          # of the warm-up + timed steps only: the extra legs below have their own peaks
+    if args.dump_outputs is not None and rank == 0:
+        # before any extra leg steps the model again; the fp32 master parameters are what the last Adam step left
+        outputs["params"] = torch.cat([p.detach().reshape(-1) for p in model.parameters() if p.requires_grad])
+        dump_outputs(outputs, args.dump_outputs)
+    outputs.clear()
     # ---- roofline leg: the SAME steps once more with a HIP-event pair around every conv / wgrad launch on the engine's stream (the
     # per-kernel launch durations of the roofline block; rocprofv3's kernel statistics of this command must agree, profiles/).  Its wall
     # time is reported as `with_launch_events` and is never `value`
     timing_log, ev_leg = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         n1 = args.steps if args.steps <= 4 else max(4, args.steps // 4)
         eng.timing = []
         if dist_on:
@@ -297,7 +334,7 @@ def main():
     # ---- extra leg (never `value`): the same step with the host -> device copy of the batch inside it (SURVEY 8d counts it; the
     # bench contract wants inputs resident).  Pinned host buffers, a few steps.
     h2d = None
-    if not args.no_h2d_leg and world == 1:
+    if args.full and not args.no_h2d_leg and world == 1:
         host = tuple(t.cpu().pin_memory() for t in (x, hr, mask, k))
         n2 = max(2, min(5, args.steps))
         step()
@@ -313,7 +350,7 @@ def main():
 
     # ---- extra leg (never `value`): the same step in the OTHER detector precision mode, a few steps, so both numbers come from one run
     other_prec = None
-    if not args.no_other_precision_leg and world == 1:
+    if args.full and not args.no_other_precision_leg and world == 1:
         alt = "fp16" if args.detector_precision == "split" else "split"
         model.detector_precision = alt
         torch.cuda.reset_peak_memory_stats(dev)
@@ -435,7 +472,7 @@ def main():
                                   exposed_all_reduce_ms_max=max(exposed, default=0.0))
         if other:
             out["step_roofline"] = None          # the folded-work figures above are config 2's
-        if not args.no_cpu_baseline and world == 1 and not other:
+        if args.full and not args.no_cpu_baseline and world == 1 and not other:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_lr, threads=args.cpu_baseline_threads)
         print(json.dumps(out))
     if dist_on:

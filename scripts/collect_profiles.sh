@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py $EXTRA --dump-layers $O/layers.json > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py $EXTRA --full --dump-layers $O/layers.json > $O/bench.json 2> $O/bench.err
 # the stats pass runs EXACTLY the steps the JSON reports (no H2D leg, no other-precision leg): per-step launch counts = calls / (steps + warmup)
 timeout -s KILL 900 rocprofv3 --kernel-trace --stats -d $O/stats -o bench --output-format csv -- python3 $R/bench.py $EXTRA --no-cpu-baseline --no-h2d-leg --no-other-precision-leg --no-kernel-timing > $O/bench_under_rocprof.json 2> $O/stats.err
 PM="$EXTRA --batch 4 --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-h2d-leg --no-other-precision-leg"

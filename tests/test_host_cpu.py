@@ -315,6 +315,23 @@ def test_bench_refuses_a_rank_count_it_cannot_run():
     assert r.returncode != 0 and "visible" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_dump_outputs_writes_float32_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: small tensors whole, larger ones as the same seeded sample of positions in every run, all float32."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    big = torch.randn(2, 3, 40, 40, generator=torch.Generator().manual_seed(0))
+    for d in ("a", "b"):
+        bench.dump_outputs({"sr_preds": big, "loss": torch.tensor(0.25, dtype=torch.float64), "kernel_preds": big[:, :1, :5, :5]}, str(tmp_path / d))
+    a, b = np.load(tmp_path / "a" / "sr_preds.npy"), np.load(tmp_path / "b" / "sr_preds.npy")
+    assert a.dtype == np.float32 and a.shape == (1000,) and np.array_equal(a, b)
+    assert np.isin(a, big.numpy().reshape(-1)).all()
+    k = np.load(tmp_path / "a" / "kernel_preds.npy")
+    assert k.dtype == np.float32 and np.array_equal(k, big[:, :1, :5, :5].numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float32 and float(np.load(tmp_path / "a" / "loss.npy")) == 0.25
+
+
 def test_dropin_resolves_the_references_import_name():
     """csbsr_amd.dropin.install(): `from model.modeling.build_model import JointModelWithLoss, JointModel` -- the reference's own import line
     (train.py:30, test.py:21) -- yields this build's classes; the names it does not build raise NotImplementedError on construction; nothing
