@@ -5,6 +5,12 @@
 
 #define WG_BP 64     // pixels per reduction step
 #define WG_BN 128    // columns (tap,channel) per tile
+
+// which kernel csbsr_conv_wgrad dispatched to (csbsr_debug_last_wgrad_kernel, csbsr_debug.h): conv_wgrad_kernel<128,128> / <128,256> /
+// <64,128> / <32,128>, conv_wgrad_thin_kernel, conv_wgrad_glds_kernel<128,128> / <128,256> / <256,256>, conv_wgrad_hr_kernel,
+// conv_wgrad_glds_kernel<128,512>.  bench.py and the tests read these values: append, never renumber (tests/conv_exact_cases.py).
+enum { WGRADK_REG128 = 0, WGRADK_REG128W, WGRADK_REG64, WGRADK_REG32, WGRADK_THIN, WGRADK_GLDS128, WGRADK_GLDS128W, WGRADK_GLDS256, WGRADK_HR,
+       WGRADK_GLDS512 };
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct WgradK {

@@ -494,13 +494,13 @@ extern "C" int csbsr_conv_wgrad(const csbsr_wgrad_desc_t* d, csbsr_stream_t s) {
       return 1;
     }
     dim3 grid((k.cbtot + WG_BN - 1) / WG_BN, 1, d->splits);
-    g_last_wgrad_kernel = 4;
+    g_last_wgrad_kernel = WGRADK_THIN;
     if (g_wgrad_use_tr) hipLaunchKernelGGL((conv_wgrad_thin_kernel<true>), grid, dim3(256), 0, st, k);
     else hipLaunchKernelGGL((conv_wgrad_thin_kernel<false>), grid, dim3(256), 0, st, k);
     CSBSR_LAUNCH_CHECK("csbsr_conv_wgrad(thin)");
     return 0;
   }
-  if (wgrad_hr_eligible(d)) { g_last_wgrad_kernel = 8; return wgrad_hr_launch(d, st); }
+  if (wgrad_hr_eligible(d)) { g_last_wgrad_kernel = WGRADK_HR; return wgrad_hr_launch(d, st); }
   // LDS-DMA kernel for every problem with > 64 A-channels.  (While its DMA pieces were the compiler's global_load_lds builtin, hipcc put
   // an s_waitcnt vmcnt(0) before each stage's first transposing read and the ring never overlapped: the kernel then only matched the
   // register-staged one at equal tile size.  With the pieces as inline assembly, N = 4: SFT 825->384 747 -> 884 TF/s, 384->825 712 -> 808,
@@ -508,7 +508,7 @@ extern "C" int csbsr_conv_wgrad(const csbsr_wgrad_desc_t* d, csbsr_stream_t s) {
   const bool glds_all = wgrad_glds_eligible(k) && (g_wgrad_glds & 8);
   if (wgrad_glds_eligible(k) && (glds_all || wgrad_glds_tile_a(k) == 256)) {
     const int ta = wgrad_glds_tile_a(k), tn = wgrad_glds_tile_n(k);
-    g_last_wgrad_kernel = ta == 256 ? 7 : (tn == 512 ? 9 : (tn == 256 ? 6 : 5));
+    g_last_wgrad_kernel = ta == 256 ? WGRADK_GLDS256 : (tn == 512 ? WGRADK_GLDS512 : (tn == 256 ? WGRADK_GLDS128W : WGRADK_GLDS128));
     k.ca_real = 0;
     if (ta != 256) {
       wgrad_locality(k, ta, tn, d->splits);
@@ -535,11 +535,11 @@ extern "C" int csbsr_conv_wgrad(const csbsr_wgrad_desc_t* d, csbsr_stream_t s) {
     return launch_wgrad<32, 128, 1, 4>(k2, d->splits, st);
   }
   if (d->ca > 64) {
-    if (wgrad_tile_n(d->ca, k.ktot, k.tap_perm != 0) == 256) { g_last_wgrad_kernel = 1; return launch_wgrad<128, 256, 2, 4>(k, d->splits, st); }
-    g_last_wgrad_kernel = 0;
+    if (wgrad_tile_n(d->ca, k.ktot, k.tap_perm != 0) == 256) { g_last_wgrad_kernel = WGRADK_REG128W; return launch_wgrad<128, 256, 2, 4>(k, d->splits, st); }
+    g_last_wgrad_kernel = WGRADK_REG128;
     return launch_wgrad<128, 128, 2, 2>(k, d->splits, st);
   }
-  if (d->ca > 32) { g_last_wgrad_kernel = 2; return launch_wgrad<64, 128, 2, 2>(k, d->splits, st); }
-  g_last_wgrad_kernel = 3;
+  if (d->ca > 32) { g_last_wgrad_kernel = WGRADK_REG64; return launch_wgrad<64, 128, 2, 2>(k, d->splits, st); }
+  g_last_wgrad_kernel = WGRADK_REG32;
   return launch_wgrad<32, 128, 1, 4>(k, d->splits, st);
 }

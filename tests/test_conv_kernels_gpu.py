@@ -719,7 +719,8 @@ def test_phase_decomposed_dgrad_takes_over_the_epilogue_backward(H, W, frozen):
     (128, 128, 19, 45, "lrelu"),            # ragged tiles on both axes, two 64-channel chunks
     (384, 825, 16, 32, "lrelu"),            # SFT conv0 shape: 6 chunks, 7 cout tiles (the last one 57 wide)
     (825, 384, 9, 40, "none_fma"),          # SFT conv1 shape: 825 -> 832 padded input channels (13 chunks), out = conv + res * res2
-    (192, 100, 24, 33, "relu_add"),         # three chunks (odd: the chunk buffers alternate across tiles), padded couts, residual add
+    (192, 100, 24, 33, "relu_add"),         # three chunks (odd: the chunk buffers alternate across chunks), padded couts, residual add (12 tiles: one per
+                                            # workgroup here -- the multi-tile walk runs under CU budgets in tests/test_conv_exact_gpu.py)
     (256, 256, 8, 64, "none"),
 ])
 def test_wide_3x3_kernel(cin, cout, H, W, mode):
@@ -778,7 +779,7 @@ def test_wide_3x3_kernel(cin, cout, H, W, mode):
     (825, 384, 9, 40, "none_fma"),          # SFT conv1 shape (shift branch): 825 -> 832 padded input channels (26 chunks), out = conv + res * res2
     (825, 384, 8, 64, "sigmoid"),           # SFT conv1 shape (scale branch)
     (192, 100, 24, 133, "relu_add"),        # six chunks, three tile columns, padded couts, residual add
-    (96, 256, 8, 64, "none"),               # three chunks (odd: the V buffers alternate across tiles)
+    (96, 256, 8, 64, "none"),               # three chunks (odd: the V buffers alternate across chunks; 8 tiles, one per workgroup)
     (256, 256, 12, 128, "none"),
 ])
 def test_wide_3x3_winograd_kernel(cin, cout, H, W, mode):
@@ -1187,7 +1188,8 @@ def test_split_precision_forward_conv(case, fused):
     (512, 64, 19, 70, "lrelu"),             # ragged tiles on both axes (two tile columns), 16 chunks
     (505, 64, 16, 64, "none_add"),          # blur_skip conv1 shape: 505 -> 512 padded input channels, residual add
     (505, 64, 9, 130, "sigmoid"),           # three tile columns, the general (non-straight-line) epilogue row
-    (96, 40, 8, 64, "relu"),                # three chunks (odd: the halo buffers alternate across tiles), 40 -> 40 padded couts
+    (96, 40, 8, 64, "relu"),                # three chunks (odd: the halo buffers alternate across chunks; 2 tiles, one per workgroup -- the
+                                            # multi-tile walk runs under CU budgets in tests/test_conv_exact_gpu.py), 40 -> 40 padded couts
     (288, 64, 24, 33, "none"),
     (64, 505, 19, 70, "lrelu"),             # the WIDE form (8 x 32 pixels x 128 couts, two workgroups per CU): blur_skip conv0 shape, ragged tiles
     (128, 200, 9, 40, "none_add"),          # four chunks, 200 -> 256 padded weight rows (the second cout tile half empty), residual add
