@@ -6,15 +6,18 @@ import numpy as np
 import torch
 
 from .data.patch_sampler import JointPatch
-from .utils.estimate_metrics import psnr_ssim, iou_sweep
+from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
 
 @torch.no_grad()
-def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, masks, kernel_targets, ksize, thresholds=THRESHOLDS):
+def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, masks, kernel_targets, ksize, thresholds=THRESHOLDS,
+                   surface_distance=False):
     """imgs [B, nPatch, 3, h, w] LR patches (as CrackDataSetTest delivers them), kernel_targets [B, nPatch, K, K];
-    returns dict(sr_preds, segment_preds, psnr [B], ssim [B], kernel_psnr [B*nPatch], iou [B, T]) -- numpy arrays for the metrics."""
+    returns dict(sr_preds, segment_preds, psnr [B], ssim [B], kernel_psnr [B*nPatch], iou [B, T]) -- numpy arrays for the metrics.
+    surface_distance=True adds hd [B, T], msd [B, T] (float64) and the counters hd_outliers, msd_outliers of calc_distance_metrics
+    (inference.py:293-336) at the same thresholds."""
     joint = JointPatch()
     imgs = imgs.view(-1, *imgs.shape[2:])
     kernel_targets = kernel_targets.view(-1, 1, *kernel_targets.shape[2:])
@@ -27,5 +30,8 @@ def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, 
     ps, ss = psnr_ssim(sr_preds, sr_targets)
     kps, _ = psnr_ssim(kernel_preds, kernel_targets)
     iou = iou_sweep(segment_preds, masks, thresholds)
-    return dict(sr_preds=sr_preds, segment_preds=segment_preds, kernel_preds=kernel_preds, psnr=ps.cpu().numpy(), ssim=ss.cpu().numpy(),
-                kernel_psnr=kps.cpu().numpy(), iou=iou.cpu().numpy())
+    out = dict(sr_preds=sr_preds, segment_preds=segment_preds, kernel_preds=kernel_preds, psnr=ps.cpu().numpy(), ssim=ss.cpu().numpy(),
+               kernel_psnr=kps.cpu().numpy(), iou=iou.cpu().numpy())
+    if surface_distance:
+        out.update(surface_distance_sweep(segment_preds, masks, thresholds))
+    return out

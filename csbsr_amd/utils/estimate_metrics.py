@@ -84,3 +84,157 @@ class IoU:
             outs = [iou_sweep(output[:, t:t + 1], target, [self.th]) for t in range(T)]
             return torch.cat(outs, 1).cpu().numpy()
         return iou_sweep(output, target, [self.th]).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------- surface distances (HD / MSD)
+# calc_distance_metrics (model/engine/inference.py:293-336) on top of model/utils/metrics/surface_distance, 2-D, spacing (1, 1).  The device
+# (csrc/surface_distance.hip) delivers, per (image, threshold, direction), integer counts keyed by  d^2 * 4 + length class ; everything
+# floating-point happens below, in fp64, as a function of those integers alone.
+
+def contour_class_table():
+    """length class (0 .. 3) of each of the 16 neighbour codes  8 m[i-1,j-1] + 4 m[i-1,j] + 2 m[i,j-1] + m[i,j]  of a corner: marching
+    squares joins the midpoints of the cell edges whose two pixels differ -- one or three pixels set: one diagonal between adjacent edge
+    midpoints (class 1); two adjacent pixels: one straight segment across the cell (2); two opposite pixels: two diagonals (3)."""
+    cls = np.zeros(16, np.int64)
+    for code in range(16):
+        n = bin(code).count("1")
+        if n in (1, 3):
+            cls[code] = 1
+        elif n == 2:
+            cls[code] = 3 if code in (0b1001, 0b0110) else 2
+    return cls
+
+
+_HALF_DIAG = float(np.hypot(0.5, 0.5))                       # midpoint of one cell edge to the midpoint of an adjacent one
+CLASS_LENGTH = np.array([0.0, _HALF_DIAG, 1.0, 2.0 * _HALF_DIAG])
+
+
+def contour_length_table():
+    """contour length of each neighbour code at unit spacing (fp64 [16])."""
+    return CLASS_LENGTH[contour_class_table()]
+
+
+# a bin's total length is  count * (u * sqrt(1/2) + v)  with integer (u, v): the running sums stay integers until one final fp64 expression
+_CLASS_U = np.array([0, 1, 0, 2], np.int64)
+_CLASS_V = np.array([0, 0, 1, 0], np.int64)
+
+
+def _finish_tables(table, keys, counts, ntab, frac):
+    """per table t < ntab, from its integer bins (rows with table == t, any order, >= 1 row each): the percentile distance -- the first bin,
+    in (d^2, class) order, whose cumulative contour length reaches ``frac`` of the table's -- , sum d * len and sum len (fp64 [ntab] each)."""
+    table, keys, counts = (np.asarray(a, np.int64) for a in (table, keys, counts))
+    order = np.argsort((table << 32) | keys)                  # by (table, key); keys are < 2^31
+    t, k, c = table[order], keys[order], counts[order]
+    start = np.searchsorted(t, np.arange(ntab))
+    assert np.array_equal(t[start], np.arange(ntab)), "every table needs at least one bin"
+    last = np.append(start[1:], len(t)) - 1
+    cls = k & 3
+    d = np.sqrt((k >> 2).astype(np.float64))
+    u, v = c * _CLASS_U[cls], c * _CLASS_V[cls]
+    cu, cv = np.cumsum(u), np.cumsum(v)
+    cu, cv = cu - (cu[start] - u[start])[t], cv - (cv[start] - v[start])[t]          # running sums within each table
+    cum = cu * _HALF_DIAG + cv
+    total = cum[last]
+    reached = np.where(cum / total[t] >= frac, np.arange(len(t)), len(t))
+    idx = np.minimum(np.minimum.reduceat(reached, start), last)
+    return d[idx], np.add.reduceat(d * (u * _HALF_DIAG + v), start), total
+
+
+def surface_metrics_from_counts(gt_to_pred, pred_to_gt, percent=50.0, max_img_len=0):
+    """HD(percent) and MSD of one (image, threshold) cell from its integer counts.  Each direction is (keys, counts): keys = d^2 * 4 + length
+    class of the border corners of one contour against the other, in any order (distinct or not), counts their multiplicities; an empty pair
+    = that contour has no border corner.  Returns (hd, msd, hd_outlier, msd_outlier) with the reference's degenerate rules: neither contour
+    -> 0; exactly one -> max_img_len and an outlier count each."""
+    ng, npd = len(gt_to_pred[0]), len(pred_to_gt[0])
+    if ng == 0 and npd == 0:
+        return 0.0, 0.0, 0, 0
+    if ng == 0 or npd == 0:
+        return float(max_img_len), float(max_img_len), 1, 1
+    table = np.concatenate([np.zeros(ng, np.int64), np.ones(npd, np.int64)])
+    perc, sdl, tot = _finish_tables(table, np.concatenate([gt_to_pred[0], pred_to_gt[0]]), np.concatenate([gt_to_pred[1], pred_to_gt[1]]),
+                                    2, percent / 100.0)
+    return float(perc.max()), float(sdl[0] / tot[0] + sdl[1] / tot[1]) / 2, 0, 0
+
+
+def _pow2_above(n):
+    return 1 << int(2 * n - 1).bit_length() if n > 0 else 0            # a power of two >= 2 n: load factor <= 1/2
+
+
+def surface_distance_sweep(segment_preds, masks, thresholds, percent=50.0, workspace_bytes=256 << 20):
+    """HD(percent) and MSD between the contours of (masks > 0.5) and (segment_preds - t > 0) for every threshold:
+    dict(hd [B,T] float64, msd [B,T] float64, hd_outliers int, msd_outliers int) -- calc_distance_metrics of the reference (whose percent is
+    50 although it prints "HD95"; its max_img_len for degenerate cells is the WIDTH, np.max(preds.shape[3:])).  ``workspace_bytes`` bounds
+    the per-chunk device workspace (column-scan planes + count tables); the thresholds of an image are processed in chunks that fit."""
+    L.load()
+    p = _dev32(segment_preds)
+    m = _dev32(masks, p)
+    H, W = int(p.shape[-2]), int(p.shape[-1])
+    p, m = p.reshape(-1, H, W), m.reshape(-1, H, W)
+    B = p.shape[0]
+    assert m.shape[0] == B, "one mask per prediction map"
+    th = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)          # == torch.Tensor(thresholds): fp32 roundings
+    assert bool((th[1:] > th[:-1]).all()), "thresholds must ascend"
+    T = th.numel()
+    dev = p.device
+    th = th.to(dev)
+    st = _stream(p)
+    ncorner = (H + 1) * (W + 1)
+    i32, u8 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.uint8, device=dev)
+    lvl, gt = torch.empty(H * W, **u8), torch.empty(H * W, **u8)
+    gcol0, dgt = torch.empty(ncorner, dtype=torch.int16, device=dev), torch.empty(ncorner, **i32)
+    hd, msd = np.zeros((B, T)), np.zeros((B, T))
+    hd_out = msd_out = 0
+    empty = (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    for b in range(B):
+        counts, rowflag = torch.zeros(T + 2, **i32), torch.zeros(H + 1, **i32)
+        L.call("csbsr_surface_prepare", _ptr(p[b]), _ptr(m[b]), _ptr(th), H, W, T, _ptr(lvl), _ptr(gt), _ptr(counts), _ptr(rowflag),
+               _ptr(gcol0), _ptr(dgt), st)
+        c = counts.cpu().numpy().astype(np.int64)
+        n_gt, n_pred = int(c[0]), np.cumsum(c[1:T + 1])
+        caps = np.zeros((T, 2), np.int64)
+        for j in range(T):
+            if n_gt > 0 and n_pred[j] > 0:
+                caps[j] = _pow2_above(n_gt), _pow2_above(int(n_pred[j]))
+            else:
+                one = (np.zeros(1, np.int64), np.ones(1, np.int64))
+                hd[b, j], msd[b, j], ho, mo = surface_metrics_from_counts(one if n_gt > 0 else empty, one if n_pred[j] > 0 else empty,
+                                                                          percent, W)
+                hd_out += ho
+                msd_out += mo
+        nrows = np.where(caps[:, 0] > 0, n_gt + n_pred, 0)       # distinct bins of a cell <= its border corners
+        need = 2 * ncorner + 8 * caps.sum(1) + 12 * nrows     # bytes per threshold: a uint16 plane, (key, count) per slot, compacted rows
+        j0 = 0
+        while j0 < T:
+            if caps[j0, 0] == 0:
+                j0 += 1
+                continue
+            nj, used = 0, 0
+            while j0 + nj < T and (nj == 0 or used + need[j0 + nj] <= workspace_bytes):
+                used += need[j0 + nj]
+                nj += 1
+            if used > workspace_bytes:
+                raise L.CsbsrHipError(f"surface_distance_sweep: one threshold of a {H}x{W} image needs {used} bytes of workspace, "
+                                      f"workspace_bytes is {workspace_bytes}")
+            cap = caps[j0:j0 + nj].reshape(-1)
+            off = np.concatenate([[0], np.cumsum(cap)[:-1]])
+            total, max_rows = int(cap.sum()), int(nrows[j0:j0 + nj].sum())
+            assert total < 2 ** 31 and max_rows < 2 ** 31
+            t_off = torch.from_numpy(off.astype(np.int32)).to(dev)
+            t_cap = torch.from_numpy(cap.astype(np.int32)).to(dev)
+            keys, cnts = torch.full((total,), -1, **i32), torch.zeros(total, **i32)
+            rows, meta = torch.empty(max_rows, 3, **i32), torch.zeros(2, **i32)
+            gcol = torch.empty(nj * ncorner, dtype=torch.int16, device=dev)
+            L.call("csbsr_surface_gather", _ptr(lvl), _ptr(gt), _ptr(dgt), _ptr(rowflag), H, W, j0, nj, _ptr(gcol), _ptr(t_off), _ptr(t_cap),
+                   _ptr(keys), _ptr(cnts), int(cap.max()), _ptr(rows), max_rows, _ptr(meta), st)
+            err, n = meta.cpu().tolist()
+            if err != 0:
+                raise L.CsbsrHipError("surface_distance_sweep: a count table overflowed")
+            r = rows[:n].cpu().numpy()
+            live = np.nonzero(cap[0::2] > 0)[0]                # the chunk's non-degenerate cells; their tables renumbered 0 .. 2 * len - 1
+            renum = np.full(2 * nj, -1, np.int64)
+            renum[2 * live], renum[2 * live + 1] = 2 * np.arange(len(live)), 2 * np.arange(len(live)) + 1
+            perc, sdl, tot = _finish_tables(renum[r[:, 0]], r[:, 1], r[:, 2], 2 * len(live), percent / 100.0)
+            hd[b, j0 + live] = np.maximum(perc[0::2], perc[1::2])
+            msd[b, j0 + live] = (sdl[0::2] / tot[0::2] + sdl[1::2] / tot[1::2]) / 2
+            j0 += nj
+    return dict(hd=hd, msd=msd, hd_outliers=int(hd_out), msd_outliers=int(msd_out))

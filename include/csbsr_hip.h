@@ -502,6 +502,24 @@ int csbsr_iou_sweep(const float* pred, const float* mask, const float* threshold
 int csbsr_psnr_ssim(const float* a, const float* b, int32_t N, int32_t C, int32_t H, int32_t W, float* sums, float* psnr, float* ssim,
                     csbsr_stream_t s);
 
+/* Surface-distance metrics of the evaluation loop (calc_distance_metrics, model/engine/inference.py:293-336, over
+ * model/utils/metrics/surface_distance): contour-to-contour distances between gt = (mask > 0.5) and pred_j = (pred - t_j > 0) for T <= 255
+ * ascending thresholds of ONE H x W image (1 .. 8191 per side), delivered as integer counts keyed by  d^2 * 4 + length class  (class 1, 2, 3 =
+ * marching-squares contour length sqrt(1/2), 1, sqrt(2) of the corner's neighbour code).  All corner-grid arrays are (H+1) x (W+1).
+ * csbsr_surface_prepare: lvl / gt = uint8 [H][W] (thresholds below the pixel; the gt bit); counts = caller-zeroed int32 [T+2]: [0] gt border
+ *   corners, [1 + k] a difference array whose prefix sum up to j is the border-corner count of pred_j; rowflag = caller-zeroed int32 [H+1]
+ *   (corner rows with a gt border corner); gcol = uint16 workspace; dgt = int32 squared distance to the nearest gt border corner.
+ * csbsr_surface_gather: thresholds j0 .. j0 + nj - 1.  gcol = uint16 [nj] corner-grid planes (workspace).  Table (jj, dir) -- dir 0: gt -> pred,
+ *   1: pred -> gt -- is tab_keys / tab_cnt [tab_off[2 jj + dir] .. + tab_cap[2 jj + dir]), cap a power of two above the cell's border-corner
+ *   count or 0 to skip the cell (max_cap = the largest); tab_keys filled with -1 and tab_cnt, meta with 0 by the caller.  Result: rows
+ *   [meta[1]][3] = (table index 2 jj + dir, key, count), every distinct key of a table once, in arbitrary order (sort by table and key);
+ *   max_rows = rows available (the sum of the cells' border-corner counts always suffices); meta[0] != 0: a table or rows was too small. */
+int csbsr_surface_prepare(const float* pred, const float* mask, const float* thresholds, int32_t H, int32_t W, int32_t T, uint8_t* lvl,
+                          uint8_t* gt, int32_t* counts, int32_t* rowflag, uint16_t* gcol, int32_t* dgt, csbsr_stream_t s);
+int csbsr_surface_gather(const uint8_t* lvl, const uint8_t* gt, const int32_t* dgt, const int32_t* rowflag, int32_t H, int32_t W, int32_t j0,
+                         int32_t nj, uint16_t* gcol, const int32_t* tab_off, const int32_t* tab_cap, int32_t* tab_keys, uint32_t* tab_cnt,
+                         int32_t max_cap, int32_t* rows, int32_t max_rows, int32_t* meta, csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
