@@ -154,6 +154,7 @@ SIGNATURES = {
     "csbsr_l1_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i64, vp, f32, vp, vp, i32, vp]),
     "csbsr_sigmoid_bwd_to_nhwc8": (i32, [vp, vp, vp, i64, f32, vp]),
     "csbsr_gaussian_kernels": (i32, [vp, vp, i32, i32, vp]),
+    "csbsr_gather_crop_u8": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]),
     "csbsr_iou_sweep": (i32, [vp, vp, vp, i32, i64, i32, f32, vp, vp, vp, vp, vp]),
     "csbsr_psnr_ssim": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "csbsr_surface_prepare": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),

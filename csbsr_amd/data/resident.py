@@ -1,0 +1,392 @@
+"""Training batches out of an HBM-resident dataset: index -> mirror -> crop -> /255 -> blur kernel -> blur -> bicubic down -> SDF.
+
+The reference feeds ``JointModelWithLoss`` from ``CrackDataSet.__getitem__`` in loader worker processes (train.py:57-63,
+model/data/crack_dataset.py:40-64): a PIL decode, numpy flips, a crop, ``image / 255``, a blur on "cuda" from inside the worker, a
+bicubic resize and a pageable fp32 copy of four tensors per sample.  Here the decoded uint8 pixels of the whole dataset live on the
+device (10^4 images of 448^2 are 6 GB of pixels + 2 GB of masks), a batch is selected by ONE kernel per pool
+(``csbsr_gather_crop_u8``, csrc/resident.hip) on the training stream, and everything after the gathered ``hr`` / ``mask`` is
+``csbsr_amd.data.degrade.DeviceDegradation`` unchanged.  Per step the host contributes a table of 32 bytes per sample through a pinned
+staging buffer: no worker process, no pixel traffic over PCIe, no host float conversion, no wait for the batch's own device work.
+
+Kernels: csbsr_gather_crop_u8 (new) + those of DeviceDegradation.  No CPU / torch fallback: batches exist on a GPU only (the pool, the
+sampler and the table validation also work on ``device="cpu"``, which is what the host-side tests use).
+"""
+import ctypes as C
+import glob
+import os
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from ..engine import _ptr
+from .degrade import DeviceDegradation
+
+# cfg.DATASET.DATA_AUGMENTATION of the shipped config/config_csbsr_pspnet.yaml (yaml's bare None arrives as the string "None")
+DEFAULT_AUGMENTATION = (("ConvertFromInts", None), ("RandomMirror", None), ("ToTensor", None), ("RandomVerticalFlip", 0.3), ("RandomCrop", None))
+
+# every name `eval(func)` resolves in model/data/transforms/transforms.py: an entry with one of these names and a non-None argument is
+# constructed and thrown away by TrainTransforms; any other name is a NameError there and a NotImplementedError here
+_REFERENCE_TRANSFORMS = frozenset((
+    "Compose", "RandomResize", "Resize", "ToTensor", "ToNumpy", "ConvertFromInts", "ConvertToInts", "SubtractMeans", "Normalize",
+    "Denormalize", "RandomSaturation", "RandomValue", "RandomHue", "RandomLightingNoise", "ConvertColor", "RandomContrast",
+    "RandomBrightness", "RandomMirror", "SwapChannels", "PhotometricDistort", "Clamp", "CenterCrop", "ConstantPadding", "MakeHeatmap",
+    "FactorResize", "RandomCrop", "PriorBox", "RandomResizedCrop", "RandomSampleCrop", "ToPercentCoords", "RandomVerticalFlip",
+    "RandomGrayscale"))
+
+
+def _is_none(a):
+    return a is None or a == "None"
+
+
+def interpret_augmentation(augmentation, crop, dims):
+    """cfg.DATASET.DATA_AUGMENTATION -> {"mirror_p", "crop"}, read the way TrainTransforms.__init__ reads it
+    (model/data/transforms/data_preprocess.py:17-28), quirks included:
+
+      ConvertFromInts, ToTensor   folded into the gather kernel (uint8 -> fp32, HWC -> CHW)
+      RandomMirror                p = 0.5 (np.random.randint(2))
+      RandomCrop                  a crop of INPUT.IMAGE_SIZE at a uniform offset; its resized_crop to the same size is the identity
+      RandomResizedCrop           scale (1, 1), ratio (1, 1) only, and only when every image already has the crop size (then it is the
+                                  identity); anything else is NotImplementedError
+      any other entry with an argument (the yaml's ["RandomVerticalFlip", 0.3])
+                                  the reference's ``else: eval(func)(args)`` constructs the transform and DROPS it: no effect there, none
+                                  here.  Vertical flips are available through DeviceTrainLoader's explicit ``vflip_p``.
+      unknown names, and argument-less transforms other than the three above
+                                  NotImplementedError
+
+    ``dims`` [n][2] are the (H, W) of the images the loader will draw from, ``crop`` = (h, w)."""
+    h, w = crop
+    out = {"mirror_p": 0.0, "crop": False}
+    for entry in augmentation:
+        func, args = entry
+        if func not in _REFERENCE_TRANSFORMS:
+            raise NotImplementedError(f"unknown augmentation {func!r}")
+        acts = func in ("RandomResizedCrop", "RandomCrop") or (_is_none(args) and func not in ("ConvertFromInts", "ToTensor"))
+        if out["crop"] and acts:           # (an entry the reference constructs and drops has no effect wherever it stands)
+            raise NotImplementedError(f"{func!r} after the crop: the gather kernel crops last")
+        if func == "RandomResizedCrop":
+            kw = args[0] if isinstance(args, (list, tuple)) else args
+            kw = dict(kw or {})
+            scale, ratio = tuple(kw.get("scale", (0.5, 1.0))), tuple(kw.get("ratio", (1.0, 1.0)))
+            if scale != (1.0, 1.0) or ratio != (1.0, 1.0) or not all(int(H) == h and int(W) == w for H, W in dims):
+                raise NotImplementedError("RandomResizedCrop is supported only where it is the identity: scale (1, 1), ratio (1, 1) and "
+                                          "every image already of the crop size")
+            out["crop"] = True
+        elif func == "RandomCrop":
+            out["crop"] = True
+        elif _is_none(args):
+            if func == "RandomMirror":
+                out["mirror_p"] = 0.5
+            elif func not in ("ConvertFromInts", "ToTensor"):
+                raise NotImplementedError(f"augmentation {func!r} is not implemented on the device path"
+                                          + (" (use vflip_p)" if func == "RandomVerticalFlip" else ""))
+        # else: constructed and dropped by the reference
+    if not out["crop"] and not all(int(H) == h and int(W) == w for H, W in dims):
+        raise ValueError("the augmentation list has no crop, so every image must already have the crop size")
+    return out
+
+
+def _as_hwc(a, channels, what):
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise TypeError(f"{what}: expected uint8, got {a.dtype}")
+    if channels == 1 and a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] != channels or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"{what}: expected H x W x {channels}, got {a.shape}")
+    return a
+
+
+class ResidentDataset:
+    """uint8 images (H x W x 3) and masks (H x W or H x W x 1) packed back to back into one contiguous device pool per kind, with an
+    int64 byte-offset table and an int32 (H, W) table.  Sizes may differ between samples, not within a pair.  ``subset`` / ``split``
+    return views on the same pools."""
+
+    def __init__(self, images, masks, device="cuda:0"):
+        if len(images) != len(masks) or len(images) == 0:
+            raise ValueError(f"{len(images)} images, {len(masks)} masks")
+        imgs = [_as_hwc(a, 3, f"image {i}") for i, a in enumerate(images)]
+        msks = [_as_hwc(a, 1, f"mask {i}") for i, a in enumerate(masks)]
+        for i, (a, m) in enumerate(zip(imgs, msks)):
+            if a.shape[:2] != m.shape[:2]:
+                raise ValueError(f"sample {i}: image {a.shape[:2]} and mask {m.shape[:2]} differ in size")
+        self.device = torch.device(device)
+        self.dims = np.array([a.shape[:2] for a in imgs], dtype=np.int32)                  # host copy: table validation
+        px = self.dims[:, 0].astype(np.int64) * self.dims[:, 1]
+        self.mask_offsets = np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64)
+        self.image_offsets = self.mask_offsets * 3
+        self.image_pool = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(self.device)
+        self.mask_pool = torch.from_numpy(np.concatenate([m.reshape(-1) for m in msks])).to(self.device)
+        self.dims_dev = torch.from_numpy(self.dims).to(self.device)
+        self.image_offsets_dev = torch.from_numpy(self.image_offsets).to(self.device)
+        self.mask_offsets_dev = torch.from_numpy(self.mask_offsets).to(self.device)
+        self.indices = np.arange(len(imgs), dtype=np.int64)                               # pool indices this view holds
+
+    @classmethod
+    def from_dirs(cls, image_dir, mask_dir, pattern="*.jpg", device="cuda:0"):
+        """Decode once with PIL: file names from ``image_dir``, the same names under ``mask_dir`` (crack_dataset.py:33-47).  Files are
+        taken as PIL decodes them, without mode conversion: an image that does not decode to 8-bit H x W x 3 (grey, palette, RGBA) or
+        a mask that does not decode to 8-bit H x W (bilevel, RGB, 16-bit) is an error that names the file.  (A palette mask decodes to
+        its 8-bit indices, here as in the reference's ``np.array(Image.open(...))``.)"""
+        from PIL import Image
+        names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(image_dir, pattern)))
+        if not names:
+            raise FileNotFoundError(f"no {pattern} under {image_dir}")
+        images, masks = [], []
+        for n in names:
+            mp = os.path.join(mask_dir, n)
+            if not os.path.isfile(mp):
+                raise FileNotFoundError(f"mask {mp} of image {os.path.join(image_dir, n)} is missing")
+            a, m = np.array(Image.open(os.path.join(image_dir, n))), np.array(Image.open(mp))          # as is, like the reference
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"image {os.path.join(image_dir, n)} decodes to {a.dtype} {a.shape}, expected 8-bit RGB (H x W x 3)")
+            if m.dtype != np.uint8 or m.ndim != 2:
+                raise ValueError(f"mask {mp} decodes to {m.dtype} {m.shape}, expected 8-bit single-channel (H x W)")
+            images.append(a)
+            masks.append(m)
+        ds = cls(images, masks, device=device)
+        ds.names = names
+        return ds
+
+    def __len__(self):
+        return len(self.indices)
+
+    @property
+    def nbytes(self):
+        return int(self.image_pool.numel() + self.mask_pool.numel())
+
+    def subset(self, indices):
+        """A view on the same pools holding ``indices`` (positions in this view)."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError("subset index out of range")
+        v = object.__new__(type(self))
+        v.__dict__.update(self.__dict__)
+        v.indices = self.indices[idx]
+        return v
+
+    def split(self, ratio, seed):
+        """Two disjoint views of int(n * ratio) and n - int(n * ratio) samples (train.py:52-57), chosen by a seeded permutation."""
+        n = len(self)
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed))).numpy()
+        k = int(n * ratio)
+        return self.subset(perm[:k]), self.subset(perm[k:])
+
+    def sample(self, i):
+        """(image H x W x 3, mask H x W x 1) uint8 numpy copies of sample ``i`` of this view."""
+        p = int(self.indices[i])
+        H, W = (int(v) for v in self.dims[p])
+        a = self.image_pool[int(self.image_offsets[p]):int(self.image_offsets[p]) + H * W * 3].cpu().numpy().reshape(H, W, 3)
+        m = self.mask_pool[int(self.mask_offsets[p]):int(self.mask_offsets[p]) + H * W].cpu().numpy().reshape(H, W, 1)
+        return a, m
+
+    def check_selection(self, sel, h, w):
+        """Raise unless every row (index, y0, x0, mirror, vflip) of ``sel`` names a pooled image and an h x w window inside it.  The
+        kernel cannot report a bad row (it clamps), so this runs on the host before every upload."""
+        s = np.asarray(sel)
+        if s.ndim != 2 or s.shape[1] != 5 or s.shape[0] < 1 or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError(f"selection table must be integer [B][5], got {s.dtype} {s.shape}")
+        s = s.astype(np.int64)
+        bad = (s[:, 0] < 0) | (s[:, 0] >= len(self.dims))
+        if bad.any():
+            raise ValueError(f"selection row {int(np.flatnonzero(bad)[0])}: image index {int(s[bad][0, 0])} outside the pool of {len(self.dims)}")
+        d = self.dims[s[:, 0]].astype(np.int64)
+        bad = (s[:, 1] < 0) | (s[:, 1] + h > d[:, 0]) | (s[:, 2] < 0) | (s[:, 2] + w > d[:, 1])
+        if bad.any():
+            r = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"selection row {r}: window y0 {int(s[r, 1])} x0 {int(s[r, 2])} of {h} x {w} leaves image {int(s[r, 0])} "
+                             f"({int(d[r, 0])} x {int(d[r, 1])})")
+        bad = ((s[:, 3] != 0) & (s[:, 3] != 1)) | ((s[:, 4] != 0) & (s[:, 4] != 1))
+        if bad.any():
+            raise ValueError(f"selection row {int(np.flatnonzero(bad)[0])}: mirror / vflip must be 0 or 1")
+
+    def gather(self, sel_dev, B, h, w):
+        """(hr [B,3,h,w], mask [B,1,h,w]) fp32 = pool bytes / 255 for the int32 [B][5] device table ``sel_dev`` (validated by the caller)."""
+        if self.device.type != "cuda":
+            raise L.CsbsrHipError("ResidentDataset.gather needs the pool on a GPU: csbsr_amd has no fallback path")
+        L.load()
+        hr = torch.empty(B, 3, h, w, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, 1, h, w, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            L.call("csbsr_gather_crop_u8", _ptr(self.image_pool), _ptr(self.image_offsets_dev), _ptr(self.dims_dev), 3, _ptr(sel_dev),
+                   B, h, w, _ptr(hr), st)
+            L.call("csbsr_gather_crop_u8", _ptr(self.mask_pool), _ptr(self.mask_offsets_dev), _ptr(self.dims_dev), 1, _ptr(sel_dev),
+                   B, h, w, _ptr(mask), st)
+        return hr, mask
+
+
+_ROW = 32          # staged bytes per sample: int32 [5] selection row, then fp32 [3] blur parameters
+_SLOTS = 4         # staging ring: a slot is rewritten four batches after its upload was enqueued
+
+
+class DeviceTrainLoader:
+    """Iterating yields ``(x_lr, hr, mask, kernels, sdf)`` on the device, the argument order of
+    ``JointModelWithLoss.forward(iter, x, sr_targets, segment_targets, kernel_targets, segment_sdf=)``.
+
+    Sampling (train.py:60-62): one permutation of the shard's samples per epoch, without replacement (RandomSampler); batches of
+    ``batch_size``, the last of an epoch short unless ``drop_last`` (BatchSampler); epochs repeat until ``num_iterations`` batches have
+    been produced (IterationBasedBatchSampler), one epoch when it is None.  ``shard=(rank, world)`` keeps the samples at positions
+    ``i % world == rank`` of ``dataset``, so data-parallel ranks see disjoint data.
+
+    Every draw comes from ONE seeded host ``torch.Generator`` (the blur parameters too: DeviceDegradation.draw_params is handed the same
+    generator).  A crop offset is uniform on [0, H-h] x [0, W-w], as torchvision's RandomCrop.get_params draws it; the mirror has p = 0.5.
+    ``draw(B)`` makes the decisions of the next batch -- a [B,5] int32 table (pool index, y0, x0, mirror, vflip) and the [B,3] blur
+    parameters (sigma_x, sigma_y, theta) -- and ``batch(sel, blur_params)`` turns decisions into tensors, so callers can force them.
+    The random streams are not NumPy's or torchvision's; the distributions are.
+
+    ``augmentation`` is a list in the format of cfg.DATASET.DATA_AUGMENTATION, by default the shipped yaml's, and is interpreted as
+    TrainTransforms does, quirks included (see interpret_augmentation): in particular the yaml's ``["RandomVerticalFlip", 0.3]`` has NO
+    effect in the reference and none here.  ``vflip_p`` is the explicit way to flip vertically and is the probability that the flip
+    HAPPENS (the reference's RandomVerticalFlip(p) class flips with probability 1 - p).  Flips act on the whole image and the window is
+    taken afterwards (RandomMirror -> ToTensor -> crop).
+
+    The mask is ``bytes / 255`` like the reference's (``mask / 255``, data_preprocess.py:44), so a {0, 255} mask becomes {0, 1}.
+    ``blur=False`` (crack_dataset.py:55-58): the kernel target is a delta at the centre, the LR image the down-scaled unblurred crop.
+    """
+
+    def __init__(self, dataset, crop, scale, ksize=21, *, batch_size, num_iterations=None, blur=True, isotropic=False, augmentation=None,
+                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1)):
+        self.dataset = dataset
+        self.h, self.w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
+        self.scale, self.K = int(scale), int(ksize)
+        if self.h < 1 or self.w < 1 or self.h % self.scale or self.w % self.scale:
+            raise ValueError(f"crop {self.h} x {self.w} must be positive multiples of the scale {self.scale}")
+        self.batch_size, self.num_iterations = int(batch_size), None if num_iterations is None else int(num_iterations)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        self.blur, self.drop_last = bool(blur), bool(drop_last)
+        self.vflip_p = float(vflip_p)
+        if not 0.0 <= self.vflip_p <= 1.0:
+            raise ValueError("vflip_p must be a probability")
+        rank, world = (int(v) for v in shard)
+        if not 0 <= rank < world:
+            raise ValueError(f"shard {shard}: need 0 <= rank < world")
+        self.indices = np.asarray(dataset.indices[rank::world], dtype=np.int64)             # pool indices of this shard
+        if len(self.indices) == 0:
+            raise ValueError(f"shard {shard} of a dataset of {len(dataset)} is empty")
+        dims = dataset.dims[self.indices]
+        if (dims[:, 0] < self.h).any() or (dims[:, 1] < self.w).any():
+            raise ValueError(f"an image is smaller than the crop {self.h} x {self.w}")
+        aug = interpret_augmentation(DEFAULT_AUGMENTATION if augmentation is None else augmentation, (self.h, self.w), dims)
+        self.mirror_p = aug["mirror_p"]
+        self.gen = torch.Generator(device="cpu")
+        if seed is not None:
+            self.gen.manual_seed(int(seed))
+        self.device = dataset.device
+        self.deg = DeviceDegradation(self.scale, ksize=self.K, isotropic=isotropic, antialias=antialias, device=self.device)
+        self.deg.gen = self.gen          # one generator for every draw
+        self.antialias = bool(antialias)
+        self._perm, self._cursor = None, 0
+        self._ring, self._slot = [None] * _SLOTS, 0
+
+    @classmethod
+    def from_cfg(cls, cfg, dataset, **kw):
+        """Arguments from a reference-style config tree: INPUT.IMAGE_SIZE, MODEL.SCALE_FACTOR, BLUR.*, SOLVER.BATCH_SIZE / MAX_ITER, and
+        DATASET.DATA_AUGMENTATION when the tree has that node (it is not in the default tree: the shipped yaml's list then applies)."""
+        args = dict(crop=tuple(cfg.INPUT.IMAGE_SIZE), scale=cfg.MODEL.SCALE_FACTOR, ksize=cfg.BLUR.KERNEL_SIZE_OUTPUT,
+                    batch_size=cfg.SOLVER.BATCH_SIZE, num_iterations=cfg.SOLVER.MAX_ITER, blur=cfg.BLUR.FLAG, isotropic=cfg.BLUR.ISOTROPIC)
+        node = cfg.get("DATASET") if hasattr(cfg, "get") else None
+        if node is not None and "DATA_AUGMENTATION" in node:
+            args["augmentation"] = node["DATA_AUGMENTATION"]
+        args.update(kw)
+        return cls(dataset, **args)
+
+    # ------------------------------------------------------------------------------------------------------------- decisions (host)
+    def _next_indices(self, B):
+        """The next <= B pool indices of the running epoch; a new permutation starts when the epoch is used up."""
+        if self._perm is None or self._cursor >= len(self._perm):
+            self._perm = self.indices[torch.randperm(len(self.indices), generator=self.gen).numpy()]
+            self._cursor = 0
+        idx = self._perm[self._cursor:self._cursor + B]
+        self._cursor += len(idx)
+        return idx
+
+    def draw(self, B=None):
+        """Decisions of the next batch: (sel int32 [b,5] = (pool index, y0, x0, mirror, vflip), blur_params fp32 [b,3]) with b <= B
+        (b < B only at the end of an epoch)."""
+        idx = self._next_indices(self.batch_size if B is None else int(B))
+        b = len(idx)
+        dims = self.dataset.dims[idx].astype(np.int64)
+        u = torch.rand(b, 4, generator=self.gen, dtype=torch.float64).numpy()
+        span_y, span_x = dims[:, 0] - self.h, dims[:, 1] - self.w
+        sel = np.empty((b, 5), dtype=np.int32)
+        sel[:, 0] = idx
+        sel[:, 1] = np.minimum((u[:, 0] * (span_y + 1)).astype(np.int64), span_y)
+        sel[:, 2] = np.minimum((u[:, 1] * (span_x + 1)).astype(np.int64), span_x)
+        sel[:, 3] = u[:, 2] < self.mirror_p
+        sel[:, 4] = u[:, 3] < self.vflip_p
+        return torch.from_numpy(sel), self.deg.draw_params(b)
+
+    # ------------------------------------------------------------------------------------------------------------- tensors (device)
+    def _upload(self, sel, params):
+        """sel int32 [B,5] + params fp32 [B,3] -> device views, through a pinned staging slot and ONE non-blocking copy.  Before a
+        slot is rewritten the host waits for the upload issued from it _SLOTS batches earlier (the pinned bytes must not change under a
+        copy in flight, as in csbsr_amd/optim.py): the only host wait on the device here, and one that blocks only a host running more
+        than _SLOTS batches ahead of the device."""
+        B = sel.shape[0]
+        slot = self._ring[self._slot]
+        if slot is None or slot[0].numel() < B * _ROW:
+            n = max(B, self.batch_size) * _ROW
+            slot = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=self.device), torch.cuda.Event()]
+            self._ring[self._slot] = slot
+        else:
+            slot[2].synchronize()          # (this slot's upload was enqueued _SLOTS batches ago: normally long consumed)
+        self._slot = (self._slot + 1) % _SLOTS
+        host, dev, ev = slot
+        host[:B * 20].view(torch.int32).view(B, 5).copy_(sel)
+        host[B * 20:B * _ROW].view(torch.float32).view(B, 3).copy_(params)
+        dev[:B * _ROW].copy_(host[:B * _ROW], non_blocking=True)
+        ev.record(torch.cuda.current_stream(self.device))
+        return dev[:B * 20].view(torch.int32).view(B, 5), dev[B * 20:B * _ROW].view(torch.float32).view(B, 3)
+
+    def batch(self, sel, blur_params=None):
+        """Decisions -> (x_lr [B,3,h/s,w/s], hr [B,3,h,w], mask [B,1,h,w], kernels [B,1,K,K], sdf [B,1,h,w]).  ``sel`` is validated on the
+        host first.  No wait on the batch's own work: the host may only block on the upload issued four batches earlier (_upload)."""
+        sel = torch.as_tensor(sel)
+        self.dataset.check_selection(sel.numpy(), self.h, self.w)
+        if self.device.type != "cuda":
+            raise L.CsbsrHipError("DeviceTrainLoader.batch needs the dataset on a GPU: csbsr_amd has no fallback path")
+        sel = sel.to(torch.int32)
+        B = sel.shape[0]
+        if self.blur:
+            if blur_params is None:
+                raise ValueError("blur=True needs the [B,3] blur parameters")
+            params = torch.as_tensor(blur_params, dtype=torch.float32).reshape(B, 3)
+        else:
+            params = torch.zeros(B, 3)
+        with torch.cuda.device(self.device):
+            sel_dev, params_dev = self._upload(sel, params)
+            hr, mask = self.dataset.gather(sel_dev, B, self.h, self.w)
+            if self.blur:
+                return self.deg(hr, mask, params=params_dev)
+            k = torch.zeros(B, 1, self.K, self.K, dtype=torch.float32, device=self.device)
+            k[:, :, self.K // 2, self.K // 2] = 1.0
+            x = torch.empty(B, 3, self.h // self.scale, self.w // self.scale, dtype=torch.float32, device=self.device)
+            L.call("csbsr_aa_bicubic_down_fwd", _ptr(hr), _ptr(x), B * 3, self.h, self.w, self.scale, int(self.antialias), self.deg._stream)
+            return x, hr, mask, k, self.deg.sdf(mask)
+
+    def __len__(self):
+        if self.num_iterations is not None:
+            return self.num_iterations
+        n = len(self.indices)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def iter_decisions(self):
+        """The (sel, blur_params) sequence __iter__ turns into batches (host only)."""
+        self._perm, produced = None, 0
+        if self.drop_last and len(self.indices) < self.batch_size:
+            return
+        while self.num_iterations is None or produced < self.num_iterations:
+            sel, params = self.draw(self.batch_size)
+            last = self._cursor >= len(self._perm)
+            if not (self.drop_last and sel.shape[0] < self.batch_size):
+                produced += 1
+                yield sel, params
+            if last and self.num_iterations is None:
+                return
+
+    def __iter__(self):
+        for sel, params in self.iter_decisions():
+            yield self.batch(sel, params)
+

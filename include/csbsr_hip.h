@@ -492,6 +492,18 @@ int csbsr_head1_bwd_input(const void* dpre, int64_t dpre_ld, const float* w, int
  * params[n] = (sigma_x, sigma_y, theta in radians): GaussianBlur.make(), model/data/blur/blur.py:121-167 (the degradation batch
  * generator, crack_dataset.py:40-64; blur + antialiased bicubic down-scaling reuse csbsr_blur_fwd / csbsr_aa_bicubic_down_fwd). */
 int csbsr_gaussian_kernels(const float* params, float* out, int32_t N, int32_t K, csbsr_stream_t s);
+/* Batch selection out of a device-resident uint8 dataset (csbsr_amd/data/resident.py): with H, W = dims[index],
+ *   out[b][c][y][x] = float(pool[offsets[index] + ((ys * W + xs) * channels + c)]) / 255      (correctly rounded fp32 division)
+ *   ys = vflip ? H-1-(y0+y) : y0+y,   xs = mirror ? W-1-(x0+x) : x0+x
+ * i.e. the flips act on the whole image and the h x w window is taken afterwards: RandomMirror -> ToTensor -> crop -> image / 255 of
+ * data_preprocess.py:17-28 and crack_dataset.py:40-50.  pool: the images back to back, each H x W x channels interleaved; offsets int64
+ * [n_img] byte offsets into pool; dims int32 [n_img][2]; channels 1 or 3; sel int32 [B][5] = (index, y0, x0, mirror, vflip), all device
+ * memory.  The caller validates sel.  The image index is the caller's responsibility ALONE: the call carries no image count, so the kernel
+ * uses sel[b][0] unchecked and an index outside the tables reads dims, offsets and pool out of bounds.  The window is defended: the
+ * kernel clamps y0 + y and x0 + x into the image, so with a valid index a bad window never reads outside its image.
+ * out fp32 [B][channels][h][w]. */
+int csbsr_gather_crop_u8(const uint8_t* pool, const int64_t* offsets, const int32_t* dims, int32_t channels, const int32_t* sel,
+                         int32_t B, int32_t h, int32_t w, float* out, csbsr_stream_t s);
 /* IoU of (pred - t_i > 0) against (mask > 0.5) for T ascending thresholds in one pass: inference.py:50-53,111-119 with
  * estimate_metrics.IoU (:64-84).  hist = caller-zeroed uint32 [N][2][T+1] workspace; iou / inter / uni are fp32 [N][T] (inter, uni
  * optional). */
