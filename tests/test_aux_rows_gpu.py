@@ -73,7 +73,11 @@ def test_checkpoint_saved_by_the_reference_drives_the_kernels():
 
 def test_patch_tiled_evaluation_step():
     """f2: one evaluation batch as inference_for_ss runs it: 2 x 2 LR patches per image through JointModel, stitched; the stitched maps
-    equal the per-patch outputs placed by hand, the metrics are finite and the threshold sweep is monotone where it must be."""
+    equal the per-patch outputs placed by hand, the metrics are finite and the threshold sweep is monotone where it must be.  The metrics
+    belong to the returned images: recomputed in fp64 (tests/metric_cases.py) from sr_preds / segment_preds / kernel_preds and the
+    targets -- PSNR and kernel-PSNR within 1e-4 dB, SSIM within 1e-5, IoU within 1 fp32 ulp of the value its integer counts give --
+    and kernel_psnr comes in b * nPatch + patch order (every patch has its own kernel target, so a permutation shows)."""
+    import metric_cases as M
     from csbsr_amd.config import cfg as base_cfg
     from csbsr_amd.modeling.build_model import JointModel
     from csbsr_amd.utils.detfill import deterministic_fill
@@ -84,7 +88,7 @@ def test_patch_tiled_evaluation_step():
     m = JointModel(cfg)
     deterministic_fill(m.state_dict())
     m.eval()
-    x, hr, mask, k = make_batch(2, 32, seed=4)                     # LR 32 -> patches of 16
+    x, hr, mask, _ = make_batch(2, 32, seed=4)                     # LR 32 -> patches of 16
     sp = SplitPatch(2, 3, 16, 16)
     patches, shapes = zip(*(sp(x[i]) for i in range(2)))
     imgs = torch.stack(patches)                                    # [B, 4, 3, 16, 16]
@@ -92,7 +96,8 @@ def test_patch_tiled_evaluation_step():
     img_shape[5:] *= 4                                             # the SR patches are 4x larger (CrackDataSetTest hands both shapes over)
     seg_shape = img_shape.copy()
     seg_shape[1], seg_shape[4] = 1, 1
-    kt = k.repeat(1, 4, 1, 1)                                      # [B, nPatch, K, K]
+    kpar = np.asarray([(0.6 + 0.4 * i, 3.4 - 0.35 * i, 0.37 * i) for i in range(8)], np.float32)
+    kt = torch.from_numpy(M.ref_gaussian_kernels(kpar, 21)).float().view(2, 4, 21, 21)      # [B, nPatch, K, K], all different
     out = evaluate_batch(m, imgs, img_shape, seg_shape, hr, mask, kt, ksize=21)
     assert tuple(out["sr_preds"].shape) == (2, 3, 128, 128) and tuple(out["segment_preds"].shape) == (2, 1, 128, 128)
     assert out["iou"].shape == (2, 99) and np.isfinite(out["iou"]).all() and np.isfinite(out["psnr"]).all() and np.isfinite(out["ssim"]).all()
@@ -104,3 +109,18 @@ def test_patch_tiled_evaluation_step():
                 tile = out["sr_preds"][b, :, iy * 64:(iy + 1) * 64, ix * 64:(ix + 1) * 64]
                 # (the patch batch of 8 and the whole-image run pick different kernels / summation orders for some layers: fp16-rounding level)
                 assert float((tile - sr_p[b * 4 + iy * 2 + ix].clamp(0, 1)).abs().max()) < 2e-3
+    # the metrics are those of the returned images
+    sr, seg, kp = out["sr_preds"].cpu().numpy(), out["segment_preds"].cpu().numpy(), out["kernel_preds"].cpu().numpy()
+    psnr, ssim = M.ref_psnr_ssim(sr, hr.numpy())
+    assert out["psnr"].shape == (2,) and np.abs(out["psnr"] - psnr).max() < 1e-4
+    assert out["ssim"].shape == (2,) and np.abs(out["ssim"] - ssim).max() < 1e-5
+    assert kp.shape == (8, 1, 21, 21)
+    kpsnr, _ = M.ref_psnr_ssim(kp, kt.view(8, 1, 21, 21).numpy())
+    assert out["kernel_psnr"].shape == (8,) and np.abs(out["kernel_psnr"] - kpsnr).max() < 1e-4
+    for perm in ([1, 0, 2, 3, 4, 5, 6, 7], [4, 5, 6, 7, 0, 1, 2, 3], [0, 1, 2, 3, 4, 5, 7, 6]):          # any other order is far outside the bound
+        other, _ = M.ref_psnr_ssim(kp, kt.view(8, 1, 21, 21)[perm].numpy())
+        assert np.abs(out["kernel_psnr"] - other).max() > 1e-2
+    from csbsr_amd.inference import THRESHOLDS
+    inter, union = M.ref_iou_counts(seg.reshape(2, -1), mask.numpy().astype(np.float32).reshape(2, -1), M.thresholds32(THRESHOLDS))
+    ref_iou = M.ref_iou(inter, union)
+    assert (np.abs(out["iou"].astype(np.float64) - ref_iou) <= M.ulp32(ref_iou)).all()
