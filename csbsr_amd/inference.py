@@ -1,11 +1,18 @@
 """Patch-tiled evaluation step on the device: the body of ``inference_for_ss``
 (model/engine/inference.py:76-119) for one batch of test images -- patches through JointModel, stitch, clip, PSNR / SSIM of the SR
 image, PSNR of the kernel, and the IoU of the segmentation map at every threshold 0.01 .. 0.99 -- without the [B,99,H,W] broadcast
-tensor and the host numpy reductions."""
+tensor and the host numpy reductions.  ``evaluate_dataset`` runs it over a whole HBM-resident test set (csbsr_amd/data/resident_test.py) and
+returns the reference's final report, with the saved images and masks leaving the device as uint8 (csrc/eval_io.hip)."""
+import csv
+import ctypes as C
+import os
+
 import numpy as np
 import torch
 
+from . import _lib as L
 from .data.patch_sampler import JointPatch
+from .engine import _ptr
 from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
@@ -34,4 +41,215 @@ def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, 
                kernel_psnr=kps.cpu().numpy(), iou=iou.cpu().numpy())
     if surface_distance:
         out.update(surface_distance_sweep(segment_preds, masks, thresholds))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ whole-test-set evaluation
+SAVE_THRESHOLD_IDX = [0] + [9 + i * 10 for i in range(9)] + [98]      # inference.py:53: the thresholds whose binary masks are saved
+CLASSIFICATION_IDX = 49                                              # inference.py:123: accuracy / sensitivity / specificity at 0.50
+_SLOTS = 3         # pinned read-back ring: a slot is rewritten three batches after its copies were enqueued, long after it was encoded
+
+
+def _stream(t):
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def stitch_clip_u8(patches, unfold_shape, clip, want_f32=True, want_u8=False):
+    """csbsr_stitch_clip_u8 on the model's patch batch [B * nH * nW, C, ph, pw] with the 1-D ``unfold_shape`` of the loader:
+    (fp32 [B,C,H,W] or None, uint8 [B,H,W,C] or None) -- JointPatch, the masked clip (``clip``) and ToPILImage's quantisation."""
+    s = [int(v) for v in unfold_shape]
+    if s[1] != 1:
+        raise L.CsbsrHipError(f"stitch_clip_u8: the channel axis is not split on the evaluation path (unfold_shape[1] = {s[1]})")
+    nH, nW, Cc, ph, pw = s[2:]
+    if not patches.is_cuda:
+        raise L.CsbsrHipError("stitch_clip_u8 needs the patches on a GPU: csbsr_amd has no fallback path")
+    p = patches.to(torch.float32).contiguous()
+    if p.numel() % (nH * nW * Cc * ph * pw) or p.numel() == 0:
+        raise ValueError(f"{tuple(patches.shape)} is not a whole number of images of unfold shape {s[1:]}")
+    B = p.numel() // (nH * nW * Cc * ph * pw)
+    f32 = torch.empty(B, Cc, nH * ph, nW * pw, dtype=torch.float32, device=p.device) if want_f32 else None
+    u8 = torch.empty(B, nH * ph, nW * pw, Cc, dtype=torch.uint8, device=p.device) if want_u8 else None
+    with torch.cuda.device(p.device):
+        L.call("csbsr_stitch_clip_u8", _ptr(p), B, Cc, nH, nW, ph, pw, int(bool(clip)), None if f32 is None else _ptr(f32),
+               None if u8 is None else _ptr(u8), _stream(p))
+    return f32, u8
+
+
+def threshold_planes_u8(pred, thresholds32):
+    """csbsr_threshold_planes_u8: uint8 [N, S, *pred.shape[1:]] = 255 where pred - t_s > 0 (fp32), for fp32 device tensors pred [N, ...] and
+    thresholds32 [S], 1 <= S <= 16."""
+    if not pred.is_cuda:
+        raise L.CsbsrHipError("threshold_planes_u8 needs the map on a GPU: csbsr_amd has no fallback path")
+    p = pred.to(torch.float32).contiguous()
+    th = thresholds32.to(p.device, torch.float32).contiguous()
+    N, S = p.shape[0], th.numel()
+    out = torch.empty(N, S, *p.shape[1:], dtype=torch.uint8, device=p.device)
+    with torch.cuda.device(p.device):
+        L.call("csbsr_threshold_planes_u8", _ptr(p), _ptr(th), N, p[0].numel(), S, _ptr(out), _stream(p))
+    return out
+
+
+def summarize(psnr, ssim, kernel_psnr, iou, hd=None, msd=None):
+    """The final report of inference_for_ss (inference.py:170-190 and plot_metrics_th) from the per-image scores, in float64: means over
+    everything, and the best threshold of the mean-over-images curve (IoU_max = max_t mean_n, HD95_min = min_t mean_n) -- not the mean of
+    per-image optima."""
+    f = lambda a: np.asarray(a, dtype=np.float64)
+    out = {"PSNR_mean": float(np.mean(f(psnr))), "SSIM_mean": float(np.mean(f(ssim))), "PSNR(Kernel)_mean": float(np.mean(f(kernel_psnr))),
+           "AIU_mean": float(np.mean(f(iou))), "IoU_max": float(np.max(np.mean(f(iou), axis=0)))}
+    if hd is not None:
+        out.update({"HD95_mean": float(np.mean(f(hd))), "MSD_mean": float(np.mean(f(msd))), "HD95_median": float(np.median(f(hd))),
+                    "MSD_median": float(np.median(f(msd))), "HD95_min": float(np.min(np.mean(f(hd), axis=0)))})
+    return out
+
+
+def write_iou_log(path, iou, thresholds, fnames):
+    """iou_log.csv (inference.py:287-289): one row per image, one column per threshold, the header row starting with an empty cell like a
+    DataFrame's index column.  Values are written with the shortest text that reads back to the same fp32; the file is not byte-identical
+    to pandas' output."""
+    iou = np.asarray(iou, dtype=np.float32)
+    assert iou.shape == (len(fnames), len(thresholds))
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow([""] + [repr(float(t)) for t in thresholds])
+        for name, row in zip(fnames, iou):
+            w.writerow([name] + [str(v) for v in row])
+
+
+def classification_counts(segment_preds, masks, threshold32):
+    """int64 device [B, 4] = (tp, tn, ground pixels, non-ground pixels) of (segment_preds - t > 0) against the mask cast to an integer the
+    way get_retinal_seg_metrics casts ``mask / 255`` to int16: 1 only where the mask byte is 255."""
+    B = segment_preds.shape[0]
+    seg = (segment_preds.reshape(B, -1) - threshold32 > 0)
+    gt = masks.reshape(B, -1).to(torch.int64) != 0
+    return torch.stack([(seg & gt).sum(1), (~seg & ~gt).sum(1), gt.sum(1), (~gt).sum(1)], dim=1)
+
+
+def classification_scores(counts):
+    """(acc, sens, spec) float64 [N] from the integer counts (retinal_metrics.py:30-62); 0 / 0 stays NaN as numpy leaves it."""
+    c = np.asarray(counts, dtype=np.int64)
+    tp, tn, ng, nn = (c[:, i].astype(np.float64) for i in range(4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        acc, sens, spec = (tp + tn) / (ng + nn), tp / ng, tn / nn
+    sens[sens == np.inf] = 1
+    spec[spec == np.inf] = 1
+    return acc, sens, spec
+
+
+class _Saver:
+    """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
+    ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
+    encodes with PIL -- the caller drains batch k after it has enqueued batch k + 1."""
+
+    def __init__(self, save_dir, thresholds):
+        self.dir = save_dir
+        self.th_names = [f"th_{thresholds[i]:.2f}" for i in SAVE_THRESHOLD_IDX if i < len(thresholds)] + ["th_-1.00"]
+        for d in ["images", "kernels", "kernels_origin"] + [os.path.join("masks", t) for t in self.th_names]:
+            os.makedirs(os.path.join(save_dir, d), exist_ok=True)
+        self.ring, self.n, self.pending = [None] * _SLOTS, 0, []
+
+    def push(self, fnames, tensors):
+        """tensors: device tensors of any dtype; their bytes go back to back into the slot's pinned buffer."""
+        need = sum(-(-t.numel() * t.element_size() // 16) * 16 for t in tensors)          # every view starts at a multiple of 16
+        slot = self.ring[self.n % _SLOTS]
+        if slot is None or slot[0].numel() < need:
+            slot = self.ring[self.n % _SLOTS] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
+        self.n += 1
+        host, ev = slot
+        views, off = [], 0
+        for t in tensors:
+            nb = t.numel() * t.element_size()
+            v = host[off:off + nb].view(t.dtype).view(t.shape)
+            v.copy_(t, non_blocking=True)
+            views.append(v)
+            off += -(-nb // 16) * 16
+        ev.record(torch.cuda.current_stream(tensors[0].device))
+        self.pending.append((fnames, views, ev))
+
+    def drain(self, keep=0):
+        from PIL import Image
+        while len(self.pending) > keep:
+            fnames, (img, raw, planes, kern), ev = self.pending.pop(0)
+            ev.synchronize()                                 # this slot's copies only
+            img, raw, planes = img.numpy(), raw.numpy(), planes.numpy()
+            nP = kern.shape[0] // len(fnames)
+            for b, name in enumerate(fnames):
+                Image.fromarray(img[b]).save(os.path.join(self.dir, "images", name))
+                for j, t in enumerate(self.th_names[:-1]):
+                    Image.fromarray(planes[b, j]).save(os.path.join(self.dir, "masks", t, name))
+                Image.fromarray(raw[b, :, :, 0]).save(os.path.join(self.dir, "masks", "th_-1.00", name))
+                stem = name.replace(".png", "")
+                for j in range(nP):                          # save_kernel: 441 values per patch, on the host
+                    k = kern[b * nP + j]
+                    for sub, tail, q in (("kernels", "", k / torch.max(k)), ("kernels_origin", "_origin", k / torch.sum(k))):
+                        q8 = torch.nan_to_num(q, nan=0.0).mul(255).byte().numpy()[0]
+                        Image.fromarray(q8).save(os.path.join(self.dir, sub, f"{stem}_{j}{tail}.png"))
+
+
+@torch.no_grad()
+def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_distance=False, classification=False, save_dir=None):
+    """``inference_for_ss`` (model/engine/inference.py:25-207) over a ``DeviceTestLoader``: per batch the computation of ``evaluate_batch``
+    -- with the stitch, the clip and the 8-bit quantisation in one kernel (csbsr_stitch_clip_u8) instead of JointPatch's copy and two masked
+    assignments -- accumulated into the reference's final report.  ``model`` is any callable with JointModel's evaluation signature.
+
+    Returns dict(fnames, psnr [N], ssim [N], kernel_psnr [N * nPatch], iou [N, T] (fp32, as evaluate_batch returns them), summary);
+    ``surface_distance`` adds hd, msd [N, T] float64 and the counters hd_outliers, msd_outliers summed over the batches;
+    ``classification`` adds acc, sens, spec [N] float64 at threshold index 49 (integer counts on the device, one fp64 division on the
+    host).  ``summary`` is ``summarize`` of those arrays.
+
+    ``save_dir`` writes what ``test.py --sf_save_image`` writes: images/<fname>, masks/th_<t:.2f>/<fname> for the threshold indices
+    [0, 9, 19, ..., 89, 98], masks/th_-1.00/<fname> for the raw map, kernels/<stem>_<j>.png, kernels_origin/<stem>_<j>_origin.png, and
+    iou_log.csv.  Images and masks leave the device as uint8 (csbsr_stitch_clip_u8, csbsr_threshold_planes_u8) through pinned slots with
+    non-blocking copies; PIL encodes batch k while the device runs batch k + 1, and the host waits on a slot's event only.  Without
+    ``save_dir`` the metrics stay on the device until the last batch has been enqueued (the surface distances, whose second half is host
+    work, excepted)."""
+    th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
+    if classification and len(thresholds) <= CLASSIFICATION_IDX:
+        raise ValueError(f"classification metrics are taken at threshold index {CLASSIFICATION_IDX}: {len(thresholds)} thresholds given")
+    saver = _Saver(save_dir, thresholds) if save_dir is not None else None
+    save_th = None
+    fnames, acc = [], {k: [] for k in ("psnr", "ssim", "kernel_psnr", "iou", "counts", "hd", "msd")}
+    hd_out = msd_out = 0
+    for imgs, sr_targets, masks, kernel_targets, names, img_shape, seg_shape in loader:
+        fnames += list(names)
+        imgs = imgs.view(-1, *imgs.shape[2:])
+        kernel_targets = kernel_targets.view(-1, 1, *kernel_targets.shape[2:])
+        dummy = torch.zeros((imgs.shape[0], 1, ksize, ksize))
+        sr_p, seg_p, kernel_preds = model(imgs, dummy, sr_targets=sr_targets)
+        sr_preds, sr_u8 = stitch_clip_u8(sr_p, img_shape, clip=True, want_u8=saver is not None)
+        segment_preds, seg_u8 = stitch_clip_u8(seg_p, seg_shape, clip=False, want_u8=saver is not None)
+        kernel_preds = kernel_preds.clamp(0, 1)
+        ps, ss = psnr_ssim(sr_preds, sr_targets)
+        kps, _ = psnr_ssim(kernel_preds, kernel_targets)
+        acc["psnr"].append(ps)
+        acc["ssim"].append(ss)
+        acc["kernel_psnr"].append(kps)
+        acc["iou"].append(iou_sweep(segment_preds, masks, thresholds))
+        if classification:
+            acc["counts"].append(classification_counts(segment_preds, masks, th32[CLASSIFICATION_IDX].to(segment_preds.device)))
+        if saver is not None:
+            if save_th is None:
+                save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(segment_preds.device)
+            planes = threshold_planes_u8(segment_preds[:, 0], save_th)
+            saver.push(list(names), [sr_u8, seg_u8, planes, kernel_preds.to(torch.float32)])
+            saver.drain(keep=1)                              # encode the batch before this one while the device runs this one
+        if surface_distance:
+            sd = surface_distance_sweep(segment_preds, masks, thresholds)
+            acc["hd"].append(sd["hd"])
+            acc["msd"].append(sd["msd"])
+            hd_out += sd["hd_outliers"]
+            msd_out += sd["msd_outliers"]
+    if not fnames:
+        raise ValueError("the test set is empty")
+    if saver is not None:
+        saver.drain()
+    out = {"fnames": fnames}
+    for k in ("psnr", "ssim", "kernel_psnr", "iou"):
+        out[k] = torch.cat(acc[k]).cpu().numpy()
+    if surface_distance:
+        out.update(hd=np.concatenate(acc["hd"]), msd=np.concatenate(acc["msd"]), hd_outliers=int(hd_out), msd_outliers=int(msd_out))
+    if classification:
+        out["acc"], out["sens"], out["spec"] = classification_scores(torch.cat(acc["counts"]).cpu().numpy())
+    out["summary"] = summarize(out["psnr"], out["ssim"], out["kernel_psnr"], out["iou"], out.get("hd"), out.get("msd"))
+    if save_dir is not None:
+        write_iou_log(os.path.join(save_dir, "iou_log.csv"), out["iou"], thresholds, fnames)
     return out

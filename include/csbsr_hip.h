@@ -504,6 +504,17 @@ int csbsr_gaussian_kernels(const float* params, float* out, int32_t N, int32_t K
  * out fp32 [B][channels][h][w]. */
 int csbsr_gather_crop_u8(const uint8_t* pool, const int64_t* offsets, const int32_t* dims, int32_t channels, const int32_t* sel,
                          int32_t B, int32_t h, int32_t w, float* out, csbsr_stream_t s);
+/* Evaluation outputs (csrc/eval_io.hip).  Stitch the model's patch batch back into images: JointPatch (patch_sampler.py:30-51), the two
+ * masked clip assignments of inference.py:94-95 and ToPILImage's mul(255).byte() with its CHW -> HWC in one pass.
+ *   patches fp32 [B][nH][nW][C][ph][pw]: patch (iy, ix) of image b is batch entry b * nH * nW + iy * nW + ix; C is 1 or 3
+ *   out_f32 [B][C][nH*ph][nW*pw]: clip != 0: v > 1 -> 1, v < 0 -> 0, everything else (NaN, -0.0) unchanged; clip == 0: v itself
+ *   out_u8  [B][nH*ph][nW*pw][C] interleaved: (uint8) trunc(clamp01(v) * 255.0f), one fp32 multiply, NaN -> 0, whatever clip is
+ * Either output may be NULL, not both. */
+int csbsr_stitch_clip_u8(const float* patches, int32_t B, int32_t C, int32_t nH, int32_t nW, int32_t ph, int32_t pw, int32_t clip,
+                         float* out_f32, uint8_t* out_u8, csbsr_stream_t s);
+/* out[n][s][i] = (pred[n][i] - thresholds[s] > 0) ? 255 : 0, the subtraction in fp32 (the predicate of inference.py:111 and of
+ * csbsr_iou_sweep), NaN -> 0.  pred fp32 [N][hw]; thresholds fp32 [S] device memory, 1 <= S <= 16, any order; out uint8 [N][S][hw]. */
+int csbsr_threshold_planes_u8(const float* pred, const float* thresholds, int32_t N, int64_t hw, int32_t S, uint8_t* out, csbsr_stream_t s);
 /* IoU of (pred - t_i > 0) against (mask > 0.5) for T ascending thresholds in one pass: inference.py:50-53,111-119 with
  * estimate_metrics.IoU (:64-84).  hist = caller-zeroed uint32 [N][2][T+1] workspace; iou / inter / uni are fp32 [N][T] (inter, uni
  * optional). */
