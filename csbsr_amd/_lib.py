@@ -6,6 +6,7 @@ crosses this boundary is a raw ``data_ptr()``.
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSBSR_LIB") or os.path.join(_HERE, "libcsbsr_hip.so")       # CSBSR_LIB: a variant build (kernel A/B experiments)
@@ -184,6 +185,47 @@ DEBUG_SIGNATURES = {
     "csbsr_debug_stream_cu_budget": (i32, [vp]),
 }
 
+# The CSBSR_* environment hooks (A/B switches), declared once: variable, default, Engine attribute + how its value is parsed, library
+# setter (csbsr_debug.h) + how its argument is parsed.  load() calls the setter of every variable that is set; Engine.__init__ sets every
+# attribute, from the default where the variable is unset.  (CSBSR_LIB, the path of a variant build, is read above.)
+Hook = namedtuple("Hook", "var default attr parse setter setter_parse", defaults=(None, None, None, None, int))
+_not0, _is1 = "0".__ne__, "1".__eq__           # the usual parse rules: on unless "0", on only for "1"
+ENV_HOOKS = (
+    Hook("CSBSR_WGRAD_DBG", setter="csbsr_debug_set_wgrad_tr"),      # bit0 transpose reads, 2 no thin, 4 no tap order, 8 no flat grid, 16 flat everywhere
+    # the library modes: 0 off, 1 default, 2 every eligible launch; the Engine flag: 0 routes the family's layers through the implicit-GEMM kernels
+    Hook("CSBSR_CONV_X3", "1", "use_x3", _not0, "csbsr_debug_set_conv_x3"),          # the wide 3x3 layers
+    # Winograd F(2,3)-along-x kernel for the wide 3x3 layers (csrc/conv_x3w.hip): built, parity-tested, 3-9 % faster per launch than the
+    # direct kernels (-9 ms per config-2 step on the SFT convs) for a composed map 13 % further from the reference --
+    # opt-in: CSBSR_CONV_X3W=1.  TWO parse rules, kept as they are: the Engine reads 0 off, "all" = 2 every eligible 3x3 layer, anything
+    # else 1 = the SFT convs (Conv.winograd); the library reads "all" as mode 1 and a number as the mode (+ 8 x min input channels / 32)
+    Hook("CSBSR_CONV_X3W", "0", "use_x3w", lambda v: {"0": 0, "all": 2}.get(v, 1), "csbsr_debug_set_conv_x3w", lambda v: 1 if v == "all" else int(v)),
+    Hook("CSBSR_CONV_X3N", "1", "use_x3n", _not0, "csbsr_debug_set_conv_x3n"),       # 0 keeps the many-channels -> <= 64-cout 3x3 layers on the LDS-DMA tiles (csrc/conv_x3n.hip)
+    Hook("CSBSR_WGRAD_HR", setter="csbsr_debug_set_wgrad_hr"),
+    Hook("CSBSR_CONV_TP", "1", "use_tp", _not0, "csbsr_debug_set_conv_tp"),          # the 2x2-tap transposed layers
+    Hook("CSBSR_CONV_GLDS", setter="csbsr_debug_set_conv_glds"),     # kernel selection experiments
+    Hook("CSBSR_CONV_HR", "1", "use_hr", _not0),                 # 0 routes the HR small-channel layers through the implicit-GEMM kernels
+    Hook("CSBSR_HEAD1", "1", "use_head1", _not0),                # 0 runs the 1-channel heads on the general conv kernels
+    Hook("CSBSR_SPLIT_FUSED", "1", "split_fused", _not0),        # 0 = the three-block split forward (x_hi staged twice)
+    Hook("CSBSR_DC_COMP", "1", "dc_comp", _not0),                # 0 = no compensation of the forward weights' fp16 rounding (Conv._dc_bias)
+    Hook("CSBSR_TAPSUM", "1", "tapsum", _not0),                  # 0 = KBPN weights rounded to nearest instead of tap-sum-preserving (Conv._wq)
+    Hook("CSBSR_WGRAD_MIRROR", "1", "wgrad_mirror", _is1),       # see Conv._bwd_weights_impl
+    Hook("CSBSR_KBUP_FUSED", "1", "thin_tp_fused", _is1),        # see Conv.bwd_thin_tp_fused (A/B timing: 0)
+    # up_conv3's epilogue-backward pass on kb.sr_reconst's dgrad (csrc/conv_thin.hip, DACT): 26 GB per step less fabric traffic, but the
+    # fused launch is no faster than the two it replaces (1065 vs 1067 ms per step, same run) -- opt-in
+    Hook("CSBSR_THIN_DACT", "0", "thin_dact", _is1),
+    Hook("CSBSR_FOLD_PRELU", "1", "fold_prelu", _is1),           # pspnet.py _blur_skip_bwd (A/B timing: 0)
+    # Weight gradients on a second HIP stream (opt-in, CSBSR_WGRAD_STREAM=1).  In the backward a layer's wgrad is a side branch (it
+    # only feeds the parameter's gradient accumulator) while the dgrad chain is the critical path; the wgrads are MFMA-bound on
+    # L2-resident tiles, much of what the chain runs between two of its convolutions is HBM-bound, so two streams could let the
+    # dispatcher fill CUs an HBM-bound kernel leaves idle.  Same kernels, same per-parameter accumulation order (all wgrads stay
+    # in program order on the side stream): bit-identical results (the GPU suite passes with it on).  Measured, round 4, same-run A/B: config 4
+    # (HRNet-OCR, hundreds of small launches) 5.57 vs 5.57 img/s; config 2 at B = 4 6.92 -> 6.88 (the big kernels each fill the
+    # chip: nothing to overlap); config 2 at B = 8 collapses to 2.4 img/s -- at 239 of 288 GB the operands the lagging side
+    # stream still holds (record_stream) leave the caching allocator without free blocks and it falls back to synchronising
+    # hipFree / hipMalloc cycles.  Hence off by default.
+    Hook("CSBSR_WGRAD_STREAM", "0", "_wg_on", _is1),
+)
+
 _lib = None
 
 
@@ -205,20 +247,9 @@ def load():
             fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
     _lib = lib
-    if os.environ.get("CSBSR_WGRAD_DBG"):          # A/B hook: bit0 transpose reads, 2 no thin, 4 no tap order, 8 no flat grid, 16 flat everywhere
-        lib.csbsr_debug_set_wgrad_tr(int(os.environ["CSBSR_WGRAD_DBG"]))
-    if os.environ.get("CSBSR_CONV_X3"):            # A/B hook: 0 off, 1 default, 2 every eligible launch
-        lib.csbsr_debug_set_conv_x3(int(os.environ["CSBSR_CONV_X3"]))
-    if os.environ.get("CSBSR_CONV_X3W"):           # A/B hook: 0 off, 1 default, 2 every eligible launch (+ 8 x min input channels / 32)
-        lib.csbsr_debug_set_conv_x3w(1 if os.environ["CSBSR_CONV_X3W"] == "all" else int(os.environ["CSBSR_CONV_X3W"]))
-    if os.environ.get("CSBSR_CONV_X3N"):           # A/B hook: 0 off, 1 default, 2 every eligible launch
-        lib.csbsr_debug_set_conv_x3n(int(os.environ["CSBSR_CONV_X3N"]))
-    if os.environ.get("CSBSR_WGRAD_HR"):           # A/B hook: 0 off, 1 default, 2 every eligible launch
-        lib.csbsr_debug_set_wgrad_hr(int(os.environ["CSBSR_WGRAD_HR"]))
-    if os.environ.get("CSBSR_CONV_TP"):            # A/B hook: 0 off, 1 default, 2 every eligible launch
-        lib.csbsr_debug_set_conv_tp(int(os.environ["CSBSR_CONV_TP"]))
-    if os.environ.get("CSBSR_CONV_GLDS"):          # A/B hook for kernel selection experiments
-        lib.csbsr_debug_set_conv_glds(int(os.environ["CSBSR_CONV_GLDS"]))
+    for h in ENV_HOOKS:
+        if h.setter and os.environ.get(h.var):
+            getattr(lib, h.setter)(h.setter_parse(os.environ[h.var]))
     return lib
 
 

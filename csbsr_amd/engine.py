@@ -15,10 +15,12 @@ PyTorch is used for device memory and the current HIP stream only.
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import torch
 
 from . import _lib as L
+from .utils.kernel_names import HEAD1_BWD_INPUT, HEAD1_FWD
 
 
 def pad8(c):
@@ -56,9 +58,8 @@ class FM:
         return self.t.stride(2)
 
     def strides(self):
-        if self.bcast:
-            return self.t.stride(0), 0, 0
-        return self.t.stride(0), self.t.stride(1), self.t.stride(2)
+        sn, sy, sx, _ = self.t.stride()
+        return (sn, 0, 0) if self.bcast else (sn, sy, sx)
 
     def seg(self):
         sn, sy, sx = self.strides()
@@ -115,39 +116,25 @@ class Engine:
         self._ws = None
         self._red = _reduction_scratch(self.device) if torch.cuda.is_available() else None
         self.training = True
-        self.use_hr = os.environ.get("CSBSR_CONV_HR", "1") != "0"       # A/B hook: 0 routes the HR small-channel layers through the implicit-GEMM kernels
-        # Winograd F(2,3)-along-x kernel for the wide 3x3 layers (csrc/conv_x3w.hip): built, parity-tested, 3-9 % faster per launch than the
-        # direct kernels (−9 ms per config-2 step on the SFT convs) for a composed map 13 % further from the reference --
-        # opt-in: CSBSR_CONV_X3W=1
-        self.use_x3w = {"0": 0, "all": 2}.get(os.environ.get("CSBSR_CONV_X3W", "0"), 1)      # 0 off, 1 the SFT convs (Conv.winograd), "all": every eligible 3x3 layer
-        self.use_x3n = os.environ.get("CSBSR_CONV_X3N", "1") != "0"     # A/B hook: 0 keeps the many-channels -> <= 64-cout 3x3 layers on the LDS-DMA tiles (csrc/conv_x3n.hip)
-        self.use_head1 = os.environ.get("CSBSR_HEAD1", "1") != "0"       # A/B hook: 0 runs the 1-channel heads on the general conv kernels
-        self.use_x3 = os.environ.get("CSBSR_CONV_X3", "1") != "0"       # A/B hook: 0 routes the wide 3x3 layers through the implicit-GEMM kernels
-        self.use_tp = os.environ.get("CSBSR_CONV_TP", "1") != "0"       # A/B hook: 0 routes the 2x2-tap transposed layers through the implicit-GEMM kernels
-        self.split_fused = os.environ.get("CSBSR_SPLIT_FUSED", "1") != "0"   # A/B hook: 0 = the three-block split forward (x_hi staged twice)
-        self.dc_comp = os.environ.get("CSBSR_DC_COMP", "1") != "0"           # A/B hook: 0 = no compensation of the forward weights' fp16 rounding (Conv._dc_bias)
-        self.tapsum = os.environ.get("CSBSR_TAPSUM", "1") != "0"             # A/B hook: 0 = KBPN weights rounded to nearest instead of tap-sum-preserving (Conv._wq)
-        # Weight gradients on a second HIP stream (opt-in, CSBSR_WGRAD_STREAM=1).  In the backward a layer's wgrad is a side branch (it
-        # only feeds the parameter's gradient accumulator) while the dgrad chain is the critical path; the wgrads are MFMA-bound on
-        # L2-resident tiles, much of what the chain runs between two of its convolutions is HBM-bound, so two streams could let the
-        # dispatcher fill CUs an HBM-bound kernel leaves idle.  Same kernels, same per-parameter accumulation order (all wgrads stay
-        # in program order on the side stream): bit-identical results (the GPU suite passes with it on).  Measured, round 4, same-run A/B: config 4
-        # (HRNet-OCR, hundreds of small launches) 5.57 vs 5.57 img/s; config 2 at B = 4 6.92 -> 6.88 (the big kernels each fill the
-        # chip: nothing to overlap); config 2 at B = 8 collapses to 2.4 img/s -- at 239 of 288 GB the operands the lagging side
-        # stream still holds (record_stream) leave the caching allocator without free blocks and it falls back to synchronising
-        # hipFree / hipMalloc cycles.  Hence off by default.
-        self.wgrad_mirror = os.environ.get("CSBSR_WGRAD_MIRROR", "1") == "1"      # see Conv._bwd_weights_impl
-        self.thin_tp_fused = os.environ.get("CSBSR_KBUP_FUSED", "1") == "1"       # see Conv.bwd_thin_tp_fused (A/B timing: 0)
-        # up_conv3's epilogue-backward pass on kb.sr_reconst's dgrad (csrc/conv_thin.hip, DACT): 26 GB per step less fabric traffic, but the
-        # fused launch is no faster than the two it replaces (1065 vs 1067 ms per step, same run) -- opt-in
-        self.thin_dact = os.environ.get("CSBSR_THIN_DACT", "0") == "1"
-        self.fold_prelu = os.environ.get("CSBSR_FOLD_PRELU", "1") == "1"        # pspnet.py _blur_skip_bwd (A/B timing: 0)
+        for h in (h for h in L.ENV_HOOKS if h.attr):            # the A/B switches (use_hr, use_x3, ..., thin_dact, _wg_on): see _lib.ENV_HOOKS
+            setattr(self, h.attr, h.parse(os.environ.get(h.var, h.default)))
         self.wg_stream = None
-        self._wg_on = os.environ.get("CSBSR_WGRAD_STREAM", "0") == "1"
         self._ws_by_stream = {}
         self._zero_blk, self._zero_off, self._zero_key, self._zero_by_stream = None, 0, None, {}
         self._probe_epoch = 0
-        self.timing = None              # list of (kind, flops, bytes, start_event, end_event) when profiling is on
+        self.timing = None              # list of (kind, flops, bytes, start_event, end_event, layer, shape, kernel id, ...) when profiling is on
+
+    def tic(self):           # start of a timed launch: its recorded start event, or None -- at the cost of this one test -- with profiling off
+        if self.timing is None:
+            return None
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return ev
+
+    def toc(self, ev0, kind, flops, nbytes, *tail):          # end of the launch ``tic`` started (ev0 is not None): its ``timing`` entry
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev1.record()
+        self.timing.append((kind, flops, nbytes, ev0, ev1) + tail)
 
     @property
     def stream(self):
@@ -297,6 +284,91 @@ class Engine:
                _ptr(drop), self.stream)
 
 
+# ---------------------------------------------------------------------------------------------- conv kernel dispatch
+
+# Which block of the master weight a launch multiplies, built once by the public method that knows it: ``kind`` 0 forward, 1 flipped
+# (stride-1 dgrad), 2 the strided / transposed form; ``c_real`` input channels x ``rows_real`` output rows of the launch, which start at
+# row ``row_off`` / channel ``k_off`` of the layer's weight.
+WBlock = namedtuple("WBlock", "kind c_real rows_real row_off k_off")
+
+# What the gates below test of one launch: ``op`` the public method ("fwd", "dgrad" = bwd_input, "folded", "classbias", "const" =
+# fwd_const_1x1), ``sp`` the layer's input is a split (hi + lo) map, ``hp`` a dgrad against [w_hi | w_lo], ``tr`` the transposed form,
+# ``stat`` the stat_mode (None without a statistics buffer), ``plan`` the split plan (Conv._split_operand), ``lo`` the launch's input is split.
+Launch = namedtuple("Launch", "op sp hp tr nseg stat dact cb_mode plan lo")
+
+# One kernel family: ``on(engine, layer)`` the Engine flag that switches it on; per op the gate (an op without one is not offered the
+# family), a pure function of those facts and of what a layer fixes at construction (k, stride, transposed, prelu): Conv keeps the answers;
+# the library's eligibility query and forward entry; the pack-cache key and the operand recipe (size query + arguments, pack entry +
+# arguments) from the WBlock, the launch's first input and padding; ``accept``: the least eligibility answer that takes the launch here.
+Family = namedtuple("Family", "on gates eligible forward key operand accept", defaults=(1,))
+
+
+def _dgrad3(c, f):          # the dgrad of a stride-1 3x3 layer, plain operands, output stored
+    return not f.hp and not c.transposed and c.stride == 1 and c.k == 3 and f.stat is None
+
+
+# many input channels -> <= 64 output channels at full resolution (PSPNet_BlurSkip's conv1's, the dgrads of its conv0's): resident pixel tile +
+# streamed fragment-ordered weights (csrc/conv_x3n.hip); a split input runs its two-product plan as 2 x Cp plain channels against [w | w]
+# (the tap-sum-rounded, pre-scaled weights repeated for the lo plane) -- so it is asked only for a plain input or the fused two-product
+# plan (5).  fwd_folded offers it even for a split layer input; bwd_input withholds it under ``dact``.
+_X3N = dict(
+    on=lambda e, c: e.use_x3n, eligible="csbsr_conv_x3n_eligible", forward="csbsr_conv_x3n_forward",
+    gates={"fwd": lambda c, f: (not c.transposed and f.nseg == 1 and c.k == 3 and c.stride == 1 and (f.stat is None or f.stat == L.STAT_BN)
+                                and (not f.lo or f.plan == 5)),
+           "dgrad": lambda c, f: _dgrad3(c, f) and not f.dact and (not f.lo or f.plan == 5),
+           "folded": lambda c, f: not f.lo or f.plan == 5},
+    key=lambda b, x: ("x3n", b.kind, b.row_off, b.k_off, b.c_real, x.cp if x.lo else 0),
+    operand=lambda c, b, x, pad: ("csbsr_packed_weight_elems_x3n", (2 * x.cp if x.lo else x.cp, b.rows_real),
+                                  "csbsr_pack_weights_x3n", (b.kind, *c.w.shape[:2], b.c_real, b.rows_real, b.row_off, b.k_off, 2 * x.cp if x.lo else x.cp,
+                                                             x.cp if x.lo else 0, c.WSCALE if x.lo else 1.0)))
+
+# The dispatch order: the first family that is switched on, whose gate passes and whose eligibility query accepts takes the launch; a
+# launch none takes goes to csbsr_conv_forward (the library's own dispatcher over the implicit-GEMM and thin kernels) with the caller's
+# packed weights.  The order is a measured decision, and the per-op differences between the gates are the ones the call sites had --
+# deliberate or not, they are kept: fwd_folded withholds x3 / x3w for a split input and does not look at the statistics mode,
+# fwd_classbias is offered conv_hr alone, fwd_const_1x1 nothing.
+FAMILIES = (
+    # the wide form of conv_x3n (answer 2) goes before conv_hr: the one launch both take -- the 32 -> 128-channel gather of a stage's thin
+    # dgrads at full resolution -- measured 4.8 -> 2.6 ms on it (csrc/conv_x3n.hip); its narrow form (answer 1) comes after conv_hr
+    Family(accept=2, **_X3N),
+    # full-resolution 32 / 49-channel 3x3 and 1x1 layers: the direct kernel (csrc/conv_hr.hip) with its own fragment-ordered weights
+    Family(lambda e, c: e.use_hr,
+           {"fwd": lambda c, f: not f.sp and not c.transposed and c.k in (1, 3) and f.nseg == 1 and c.prelu is None,
+            "dgrad": lambda c, f: not f.hp and not c.transposed and c.stride == 1 and c.k in (1, 3) and f.stat is None,
+            "classbias": lambda c, f: c.k == 1 and f.cb_mode == 1 and c.prelu is None},
+           "csbsr_conv_hr_eligible", "csbsr_conv_hr_forward", lambda b, x: ("hr", b.kind, b.row_off),
+           lambda c, b, x, pad: ("csbsr_packed_weight_elems_hr", (c.k, b.c_real, b.rows_real),
+                                 "csbsr_pack_weights_hr", (b.kind, c.k, *c.w.shape[:2], b.c_real, b.rows_real, b.row_off, 0))),
+    Family(**_X3N),
+    # wide low-resolution 3x3 stride-1 layers (SFT convs and their dgrads) as Winograd F(2, 3) along x: 2/3 of the direct kernel's MFMA
+    # work, transformed fp16 weights packed once per optimiser step (csrc/conv_x3w.hip).  Engine.use_x3w 1: the layers marked
+    # Conv.winograd, 2: every eligible one
+    Family(lambda e, c: e.use_x3w and (c.winograd or e.use_x3w == 2),
+           {"fwd": lambda c, f: not f.sp and not c.transposed and f.nseg == 1 and c.k == 3, "dgrad": _dgrad3, "folded": lambda c, f: not f.sp},
+           "csbsr_conv_x3w_eligible", "csbsr_conv_x3w_forward", lambda b, x: ("x3w", b.kind, b.row_off, b.k_off, b.c_real),
+           lambda c, b, x, pad: ("csbsr_packed_weight_elems_x3w", (b.c_real, b.rows_real),
+                                 "csbsr_pack_weights_x3w", (b.kind, *c.w.shape[:2], b.c_real, b.rows_real, b.row_off, b.k_off))),
+    # wide low-resolution 3x3 layers (SFT convs and their dgrads): per-chunk halo tile + fragment-ordered weights from L2 (csrc/conv_x3.hip)
+    # ... and the k = 2 x stride strided layers (kind 2: 8x8 stride-4 convs, dgrads of the 8x8 stride-4 deconvs): chunk = input phase
+    Family(lambda e, c: e.use_x3,
+           {"fwd": lambda c, f: not f.sp and not c.transposed and f.nseg == 1 and (c.k == 3 or c.k == 2 * c.stride),
+            "dgrad": lambda c, f: c.k == 2 * c.stride and not f.hp and f.stat is None if c.transposed else _dgrad3(c, f),
+            "folded": lambda c, f: not f.sp},
+           "csbsr_conv_x3_eligible", "csbsr_conv_x3_forward", lambda b, x: ("x3", b.kind, b.row_off, b.k_off, b.c_real),
+           lambda c, b, x, pad: (("csbsr_packed_weight_elems_x3_strided", (c.stride, b.c_real, b.rows_real),
+                                  "csbsr_pack_weights_x3_strided", (*c.w.shape[:2], c.k, c.stride, b.c_real, b.rows_real, b.row_off, b.k_off)) if b.kind == 2 else
+                                 ("csbsr_packed_weight_elems_x3", (b.c_real, b.rows_real),
+                                  "csbsr_pack_weights_x3", (b.kind, *c.w.shape[:2], b.c_real, b.rows_real, b.row_off, b.k_off)))),
+    # 2x2-tap transposed layers (8x8 stride 4 / 12x12 stride 8): resident halo tile + streamed fragment-ordered weights (csrc/conv_tp.hip)
+    Family(lambda e, c: e.use_tp,
+           {"fwd": lambda c, f: c.transposed and f.nseg == 1 and not f.sp, "dgrad": lambda c, f: f.tr and not f.hp and f.stat is None},
+           "csbsr_conv_tp_eligible", "csbsr_conv_tp_forward", lambda b, x: ("tp", b.row_off, b.k_off),
+           lambda c, b, x, pad: ("csbsr_packed_weight_elems_tp", (c.stride, b.c_real),
+                                 "csbsr_pack_weights_tp", (*c.w.shape[:2], c.k, c.k, c.stride, pad, b.c_real, b.rows_real, b.row_off, b.k_off))),
+)
+TP = FAMILIES[-1]
+
+
 # ---------------------------------------------------------------------------------------------- conv layer
 
 class Conv:
@@ -322,6 +394,7 @@ class Conv:
         self.act, self.slope = act, slope
         self.prelu = params[prelu] if prelu else None
         self._packed = {}
+        self._routes = {}            # launch facts -> the kernel families offered such a launch (_launch)
         self.hp_dgrad = False        # detector precision mode: dgrad against [w_hi | w_lo] (two MFMA passes), see bwd_input
         # detector precision mode, per layer (the model's precision plan): K blocks a forward conv of a split (hi + lo) input runs --
         # 3: x_hi w_hi + x_lo w_hi + x_hi w_lo;  2: [x_hi | x_lo] w_hi (the weight's rounding error stays);  1: x_hi w_hi, plain fp16
@@ -335,16 +408,19 @@ class Conv:
     def invalidate(self):
         self._packed.clear()
 
+    def _pack_new(self, key, src, size_sym, size_args, pack_sym, pack_args):
+        """a cache miss (once per optimiser step): pack fp32 ``src`` into the fp16 operand ``key``; ``pack_args`` go between (src, dst) and the stream"""
+        n = getattr(L.load(), size_sym)(*size_args)
+        dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
+        L.call(pack_sym, _ptr(src), _ptr(dst), *pack_args, self.eng.stream)
+        self._packed[key] = dst
+        return dst
+
     def _pack(self, key, kind, seg0, seg1, row_off, nrows, stride, pad, k_off=0):
         if key in self._packed:
             return self._packed[key]
-        D0, D1 = self.w.shape[0], self.w.shape[1]
-        n = L.load().csbsr_packed_weight_elems(kind, D0, D1, self.k, self.k, stride, seg0, seg1, nrows)
-        dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-        L.call("csbsr_pack_weights", _ptr(self._wq()), _ptr(dst), kind, D0, D1, self.k, self.k, stride, pad, seg0, seg1, row_off, nrows,
-               k_off, self.eng.stream)
-        self._packed[key] = dst
-        return dst
+        return self._pack_new(key, self._wq(), "csbsr_packed_weight_elems", (kind, *self.w.shape[:2], self.k, self.k, stride, seg0, seg1, nrows),
+                              "csbsr_pack_weights", (kind, *self.w.shape[:2], self.k, self.k, stride, pad, seg0, seg1, row_off, nrows, k_off))
 
     def _wq(self):
         """the fp32 tensor the plain-fp16 operand packs read: the master weights, or -- on the layers that carry the rounding compensation
@@ -374,36 +450,33 @@ class Conv:
     def _pack_split(self, key, kind, creal, nrows, stride, pad, k_off=0, layout=0, row_off=0, tapsum=False):
         if key in self._packed:
             return self._packed[key]
-        D0, D1 = self.w.shape[0], self.w.shape[1]
-        n = L.load().csbsr_packed_weight_elems_split(kind, D0, D1, self.k, self.k, stride, creal, nrows, layout)
-        dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
         # (layout 2 = [w_hi | w_hi], a layer whose plan drops the x_hi w_lo product: its one rounding of the weights is the tap-sum-preserving one)
-        src = self._wq() if (layout == 2 or tapsum) else self.w
-        L.call("csbsr_pack_weights_split", _ptr(src), _ptr(dst), kind, D0, D1, self.k, self.k, stride, pad, creal, row_off, nrows, k_off,
-               self.WSCALE, layout, self.eng.stream)
-        self._packed[key] = dst
-        return dst
+        return self._pack_new(key, self._wq() if (layout == 2 or tapsum) else self.w,
+                              "csbsr_packed_weight_elems_split", (kind, *self.w.shape[:2], self.k, self.k, stride, creal, nrows, layout),
+                              "csbsr_pack_weights_split", (kind, *self.w.shape[:2], self.k, self.k, stride, pad, creal, row_off, nrows, k_off, self.WSCALE, layout))
 
     def _split_operand(self, x, key, kind, creal, nrows, stride, pad, k_off=0):
-        """(input FMs, packed weights, out_scale, K blocks) of a forward conv whose input is a split map, per this layer's plan."""
-        nb = self.fwd_blocks
+        """(input FMs, packed weights, out_scale, split plan, fallback) of a forward conv over one input segment: for a split map per this
+        layer's plan.  Plan = K blocks (1 / 2 / 3), or 4 / 5: the fused three- / two-product form, for which ``fallback()`` packs the operand of
+        the three- / two-block form _launch runs instead should the library refuse the fused one for this launch
+        (csbsr_conv_split_fused_eligible: the LDS-DMA kernels switched off by a debug mode, a tile they do not take)."""
+        if not x.lo:     # a plain input: one segment of this layer's weights
+            return (x,), self._pack(key, kind, creal, 0, 0, nrows, stride, pad, k_off), 1.0, 3, None
+        nb, key = self.fwd_blocks, key + "_split"
         if nb == 1:      # the hi plane alone against plain fp16 weights
-            return (FM(x.t, x.c, H=x.H, W=x.W),), self._pack((key, 1), kind, creal, 0, 0, nrows, stride, pad, k_off), 1.0, 1
-        if nb == 3 and self.eng.split_fused and x.cp >= 32 and pad8(nrows) > 32 and kind == 0:
+            return (FM(x.t, x.c, H=x.H, W=x.W),), self._pack((key, 1), kind, creal, 0, 0, nrows, stride, pad, k_off), 1.0, 1, None
+
+        a = (kind, creal, nrows, stride, pad, k_off)
+        if self.eng.split_fused and x.cp >= 32 and pad8(nrows) > 32 and kind == 0 and nb == 3:
             # fused form (csbsr_conv_desc_t::split_fused): one staged K slice = 32 channels of [x_hi | x_lo] against [w_hi | w_lo], all three
             # products from it -- the LDS-DMA kernels' launch time follows the staged bytes, 2/3 of the three-block form's
-            # (should the library refuse the fused form for this launch -- csbsr_conv_split_fused_eligible: the LDS-DMA kernels switched off by a
-            # debug mode, a tile they do not take -- _launch falls back to the three-block operand)
-            self._fs_fallback = lambda: self._pack_split((key, 3), kind, creal, nrows, stride, pad, k_off=k_off, layout=0)
-            return (x,), self._pack_split((key, "fs"), kind, creal, nrows, stride, pad, k_off=k_off, layout=3), 1.0 / self.WSCALE, 4
-        if nb == 2 and self.eng.split_fused and x.cp >= 32 and pad8(nrows) > 32 and kind == 0:
+            return (x,), self._pack_split((key, "fs"), *a, 3), 1.0 / self.WSCALE, 4, lambda: self._pack_split((key, 3), *a, 0)
+        if self.eng.split_fused and x.cp >= 32 and pad8(nrows) > 32 and kind == 0 and nb == 2:
             # the two-product plan in the fused stage (csbsr_conv_desc_t::split_fused = 2, round 6): [x_hi | x_lo] staged once against
             # [w_hi | -] -- the two-block form below stages w_hi twice and measured no faster than the fused THREE products.  The hi halves
             # are the tap-sum-preserving rounding (a layer that keeps its weights' rounding), so the packed lo halves are zero and unread
-            self._fs_fallback = lambda: self._pack_split((key, 2), kind, creal, nrows, stride, pad, k_off=k_off, layout=2)
-            return (x,), self._pack_split((key, "fs2"), kind, creal, nrows, stride, pad, k_off=k_off, layout=3, tapsum=True), 1.0 / self.WSCALE, 5
-        wt = self._pack_split((key, nb), kind, creal, nrows, stride, pad, k_off=k_off, layout=0 if nb == 3 else 2)
-        return (x,), wt, 1.0 / self.WSCALE, nb
+            return (x,), self._pack_split((key, "fs2"), *a, 3, tapsum=True), 1.0 / self.WSCALE, 5, lambda: self._pack_split((key, 2), *a, 2)
+        return (x,), self._pack_split((key, nb), *a, 0 if nb == 3 else 2), 1.0 / self.WSCALE, nb, None
 
     def _dc_bias(self, xs):
         """bias + sum_c mean_c(x) * sum_taps (w - fp16(w))[o, c]: what the rounding of the weights to fp16 takes away from the layer's
@@ -456,186 +529,120 @@ class Conv:
                 and self.act in (L.ACT_NONE, L.ACT_SIGMOID) and f.cp in (64, 128, 256) and f.c == f.cp and not f.bcast and f.flat_ok()
                 and (f.lo in (0, f.cp)))
 
-    def _head1_w(self):
-        """the head's weight row as a contiguous fp32 vector (a view of the master weights: [1, C, 1, 1])"""
-        return self.w.reshape(-1)
-
     def out_size(self, H, W):
         k, s, p, d = self.k, self.stride, self.pad, self.dil
         if self.transposed:
             return (H - 1) * s - 2 * p + k, (W - 1) * s - 2 * p + k
         return (H + 2 * p - d * (k - 1) - 1) // s + 1, (W + 2 * p - d * (k - 1) - 1) // s + 1
 
-    def _launch(self, xs, wt, transposed, k, stride, pad, dil, H, W, OH, OW, cout, out, out32, bias, act, slope, prelu, res, res2,
-                res_mode, accumulate, stat, stat_mode, out_scale, cbias=None, mask=None, hr=None, tp=None, dact=None, x3=None, dres=None,
-                cb_mode=0, split_blocks=3, x3n=None):
-        d = L.ConvDesc()
-        x0 = xs[0]
+    def _fill_dact(self, d, lib, tp_offered, dact, dres):
+        """``dact`` = (the layer below -- a Conv with PReLU / bias --, its saved output): the fields of a dgrad that takes over that layer's
+        activation derivative AND bias / slope gradient sums from the stand-alone epilogue-backward pass.  Only the phase-decomposed
+        transposed kernel (csrc/conv_tp.hip) and the thin-input accumulating dgrad (csrc/conv_thin.hip, DACT: csbsr_conv_forward dispatches
+        it) can; where neither does, the fields are cleared again.  Returns (fused, conv_tp must not take the launch)."""
+        below, saved = dact
+        fz = getattr(below, "frozen", False)
+        d.mask, (d.m_sn, d.m_sy, d.m_sx), d.mask_slope = _ptr(saved.t), saved.strides(), float(below.slope)
+        d.mask_prelu = _ptr(below.prelu)
+        d.dact_bias = None if (below.b is None or fz) else _ptr(grad_acc(below.b))
+        d.dact_prelu = None if (below.prelu is None or fz) else _ptr(grad_acc(below.prelu))
+        if dres is not None:        # the layer below was out = act(pre) +- res: (res FM, FM receiving d(res), its res_mode)
+            rfm, dfm, rmode = dres
+            d.res_mode, d.res, (d.r_sn, d.r_sy, d.r_sx) = rmode, _ptr(rfm.t), rfm.strides()
+            d.dres, (d.dr_sn, d.dr_sy, d.dr_sx) = _ptr(dfm.t), dfm.strides()
+        if tp_offered and TP.on(self.eng, self) and lib.csbsr_conv_tp_eligible(C.byref(d)):
+            return True, False
+        if (dres is not None and self.eng.thin_dact and lib.csbsr_conv_thin_dact_eligible(C.byref(d))
+                and (below.prelu is None or self.eng.prelu_fold_ok(below.prelu))):      # (the kernel divides its slope sum by the slope)
+            return True, True
+        d.mask, d.mask_prelu, d.dact_bias, d.dact_prelu = None, None, None, None
+        if dres is not None:
+            d.res_mode, d.res, d.dres = L.RES_NONE, None, None
+        return False, False
+
+    def _launch(self, op, xs, wt, blk, transposed, pad, dil, OH, OW, *, out=None, out32=None, bias=None, epilogue=False, res=None, res2=None,
+                res_mode=L.RES_NONE, accumulate=False, stat=None, stat_mode=L.STAT_NONE, out_scale=1.0, cbias=None, cb_mode=0, mask=None,
+                dact=None, dres=None, sp=False, hp=False, plan=3, fallback=None):
+        """One convolution launch of this layer's k x k, stride-``self.stride`` taps over ``xs`` into ``blk.rows_real`` channels of OH x OW:
+        fill the descriptor, then hand it to the first kernel family of FAMILIES that takes it, else to the general kernels with the
+        caller's packed ``wt``.  ``op``: the public method (an op no gate names, None say, is offered no family); ``blk``: the WBlock the
+        launch multiplies; ``epilogue``: apply the layer's own activation; ``plan`` / ``fallback``: see _split_operand."""
+        d, lib, eng, x0, cout = L.ConvDesc(), L.load(), self.eng, xs[0], blk.rows_real
+        # ---- input segments and the split plan
         if x0.lo:                       # split-fp16 input: [hi | lo] (+ hi again for the x_hi w_lo block), weights from _pack_split
-            assert len(xs) == 1 and not transposed and split_blocks in (2, 3, 4, 5)      # 4: the fused three-product form, 5: the fused two-product form
+            assert len(xs) == 1 and not transposed and plan in (2, 3, 4, 5)
             s0, s1 = x0.split_segs()
             d.inp[0] = s0
-            if split_blocks == 3:
+            if plan == 3:
                 d.inp[1] = s1
-            d.split_fused = 1 if split_blocks == 4 else (2 if split_blocks == 5 else 0)
+            d.split_fused = 1 if plan == 4 else (2 if plan == 5 else 0)
         else:
             d.inp[0] = x0.seg()
             if len(xs) > 1:
                 d.inp[1] = xs[1].seg()
-        d.N, d.H, d.W, d.OH, d.OW = x0.N, H, W, OH, OW
-        d.transposed, d.KH, d.KW, d.stride, d.pad, d.dil = int(transposed), k, k, stride, pad, dil
-        d.wt, d.cout = _ptr(wt), cout
-        d.coutp = pad8(cout)
+        d.N, d.H, d.W, d.OH, d.OW = x0.N, x0.H, x0.W, OH, OW
+        d.transposed, d.KH, d.KW, d.stride, d.pad, d.dil = int(transposed), self.k, self.k, self.stride, pad, dil
+        d.wt, d.cout, d.coutp = _ptr(wt), cout, pad8(cout)
+        # ---- output
         if out is not None:
             assert out.cp == d.coutp and (out.H, out.W) == (OH, OW), (out.cp, d.coutp, out.H, OH)
-            sn, sy, sx = out.strides()
-            d.out16, d.o_sn, d.o_sy, d.o_sx, d.o_lo = _ptr(out.t), sn, sy, sx, out.lo
+            d.out16, (d.o_sn, d.o_sy, d.o_sx), d.o_lo = _ptr(out.t), out.strides(), out.lo
         if out32 is not None:           # fp32 NCHW planar [N, cout, OH, OW]
             assert out32.is_contiguous() and tuple(out32.shape) == (x0.N, cout, OH, OW)
             d.out32, d.o32_sn, d.o32_sy, d.o32_sx, d.o32_sc = _ptr(out32), cout * OH * OW, OW, 1, OH * OW
-        d.bias, d.cbias, d.act, d.act_slope, d.prelu = _ptr(bias), _ptr(cbias), act, slope, _ptr(prelu)
+        d.accumulate, d.stat_mode, d.stat, d.out_scale = int(accumulate), stat_mode, _ptr(stat), out_scale
+        # ---- epilogue operands
+        d.bias, d.cbias = _ptr(bias), _ptr(cbias)
+        if epilogue:
+            d.act, d.act_slope, d.prelu = self.act, self.slope, _ptr(self.prelu)
         if bias is not None and bias.dim() == 2:          # per-sample bias rows (Conv._dc_bias)
             d.bias_sn = bias.shape[1]
-        d.cbias_mode = cb_mode
-        d.res_mode = res_mode
+        d.cbias_mode, d.res_mode = cb_mode, res_mode
         if res is not None:
-            sn, sy, sx = res.strides()
-            d.res, d.r_sn, d.r_sy, d.r_sx, d.r_lo = _ptr(res.t), sn, sy, sx, res.lo
+            d.res, (d.r_sn, d.r_sy, d.r_sx), d.r_lo = _ptr(res.t), res.strides(), res.lo
         if res2 is not None:
-            sn, sy, sx = res2.strides()
-            d.res2, d.r2_sn, d.r2_sy, d.r2_sx, d.r2_lo = _ptr(res2.t), sn, sy, sx, res2.lo
-        d.accumulate, d.stat_mode, d.stat, d.out_scale = int(accumulate), stat_mode, _ptr(stat), out_scale
+            d.res2, (d.r2_sn, d.r2_sy, d.r2_sx), d.r2_lo = _ptr(res2.t), res2.strides(), res2.lo
         if mask is not None:            # (saved forward output of the consumer layer, its negative slope): see csbsr_conv_desc_t.mask
             mfm, mslope = mask
             assert out is not None and mfm.cp == d.coutp and (mfm.H, mfm.W) == (OH, OW) and not mfm.bcast
-            sn, sy, sx = mfm.strides()
+            d.mask, (d.m_sn, d.m_sy, d.m_sx) = _ptr(mfm.t), mfm.strides()
             if torch.is_tensor(mslope):      # a learned PReLU slope: read on the device (csbsr_conv_desc_t::mask_prelu)
-                d.mask, d.m_sn, d.m_sy, d.m_sx, d.mask_slope, d.mask_prelu = _ptr(mfm.t), sn, sy, sx, 0.0, _ptr(mslope)
+                d.mask_prelu = _ptr(mslope)
             else:
-                d.mask, d.m_sn, d.m_sy, d.m_sx, d.mask_slope = _ptr(mfm.t), sn, sy, sx, float(mslope)
-        if x0.lo and split_blocks in (4, 5) and not L.load().csbsr_conv_split_fused_eligible(C.byref(d)):
-            if split_blocks == 4:
-                d.split_fused, d.inp[1], d.wt, split_blocks = 0, x0.split_segs()[1], _ptr(self._fs_fallback()), 3
-            else:
-                d.split_fused, d.wt, split_blocks = 0, _ptr(self._fs_fallback()), 2
-        self.last_fused = False
-        use_tp = tp is not None and self.eng.use_tp
-        if dact is not None:
-            # the layer below (a Conv with PReLU / bias) whose activation derivative AND bias / slope gradient sums this launch would
-            # take over from the stand-alone epilogue-backward pass: only the phase-decomposed transposed kernel can (csrc/conv_tp.hip)
-            below, saved = dact
-            fz = getattr(below, "frozen", False)
-            sn, sy, sx = saved.strides()
-            d.mask, d.m_sn, d.m_sy, d.m_sx, d.mask_slope = _ptr(saved.t), sn, sy, sx, float(below.slope)
-            d.mask_prelu = _ptr(below.prelu)
-            d.dact_bias = None if (below.b is None or fz) else _ptr(grad_acc(below.b))
-            d.dact_prelu = None if (below.prelu is None or fz) else _ptr(grad_acc(below.prelu))
-            if dres is not None:        # the layer below was out = act(pre) +- res: (res FM, FM receiving d(res), its res_mode)
-                rfm, dfm, rmode = dres
-                sn, sy, sx = rfm.strides()
-                d.res_mode, d.res, d.r_sn, d.r_sy, d.r_sx = rmode, _ptr(rfm.t), sn, sy, sx
-                sn, sy, sx = dfm.strides()
-                d.dres, d.dr_sn, d.dr_sy, d.dr_sx = _ptr(dfm.t), sn, sy, sx
-            if use_tp and L.load().csbsr_conv_tp_eligible(C.byref(d)):
-                self.last_fused = True
-            elif (dres is not None and self.eng.thin_dact and L.load().csbsr_conv_thin_dact_eligible(C.byref(d))
-                  and (below.prelu is None or self.eng.prelu_fold_ok(below.prelu))):      # (the kernel divides its slope sum by the slope)
-                self.last_fused = True      # the thin-input accumulating dgrad (csrc/conv_thin.hip, DACT): csbsr_conv_forward dispatches it
-                use_tp = False
-            else:
-                d.mask, d.mask_prelu, d.dact_bias, d.dact_prelu = None, None, None, None
-                if dres is not None:
-                    d.res_mode, d.res, d.dres = L.RES_NONE, None, None
-        tm = self.eng.timing
-        if tm is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        # full-resolution 32 / 49-channel 3x3 layers: the direct kernel (csrc/conv_hr.hip) with its own fragment-ordered weights
-        # (the wide form of conv_x3n goes first: the one launch both take -- the 32 -> 128-channel gather of a stage's thin dgrads at full
-        # resolution -- measured 4.8 -> 2.6 ms on it, csrc/conv_x3n.hip)
-        xn = (L.load().csbsr_conv_x3n_eligible(C.byref(d)) if (x3n is not None and self.eng.use_x3n and (not x0.lo or split_blocks == 5)) else 0)
-        if xn != 2 and hr is not None and self.eng.use_hr and L.load().csbsr_conv_hr_eligible(C.byref(d)):
-            kind, c_real, rows_real, row_off = hr
-            key = ("hr", kind, row_off)
-            if key not in self._packed:
-                n = L.load().csbsr_packed_weight_elems_hr(k, c_real, rows_real)
-                dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-                L.call("csbsr_pack_weights_hr", _ptr(self._wq()), _ptr(dst), kind, k, self.w.shape[0], self.w.shape[1], c_real, rows_real, row_off, 0,
-                       self.eng.stream)
-                self._packed[key] = dst
-            d.wt = _ptr(self._packed[key])
-            L.call("csbsr_conv_hr_forward", C.byref(d), self.eng.stream)
-        elif xn:
-            # many input channels -> <= 64 output channels at full resolution (PSPNet_BlurSkip's conv1's, the dgrads of its conv0's): resident
-            # pixel tile + streamed fragment-ordered weights (csrc/conv_x3n.hip); a split input runs its two-product plan as 2 x Cp plain
-            # channels against [w | w] (the tap-sum-rounded, pre-scaled weights repeated for the lo plane)
-            kind, c_real, rows_real, row_off, k_off = x3n
-            plane = x0.cp if x0.lo else 0
-            in_ch = 2 * x0.cp if x0.lo else x0.cp
-            key = ("x3n", kind, row_off, k_off, c_real, plane)
-            if key not in self._packed:
-                n = L.load().csbsr_packed_weight_elems_x3n(in_ch, rows_real)
-                dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-                L.call("csbsr_pack_weights_x3n", _ptr(self._wq()), _ptr(dst), kind, self.w.shape[0], self.w.shape[1], c_real, rows_real, row_off,
-                       k_off, in_ch, plane, self.WSCALE if x0.lo else 1.0, self.eng.stream)
-                self._packed[key] = dst
-            d.wt = _ptr(self._packed[key])
-            L.call("csbsr_conv_x3n_forward", C.byref(d), self.eng.stream)
-        elif (x3 is not None and x3[0] in (0, 1) and self.eng.use_x3w and (self.winograd or self.eng.use_x3w == 2)
-              and L.load().csbsr_conv_x3w_eligible(C.byref(d))):
-            # wide low-resolution 3x3 stride-1 layers (SFT convs and their dgrads) as Winograd F(2, 3) along x: 2/3 of the direct kernel's
-            # MFMA work, transformed fp16 weights packed once per optimiser step (csrc/conv_x3w.hip)
-            kind, c_real, rows_real, row_off, k_off = x3
-            key = ("x3w", kind, row_off, k_off, c_real)
-            if key not in self._packed:
-                n = L.load().csbsr_packed_weight_elems_x3w(c_real, rows_real)
-                dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-                L.call("csbsr_pack_weights_x3w", _ptr(self._wq()), _ptr(dst), kind, self.w.shape[0], self.w.shape[1], c_real, rows_real, row_off,
-                       k_off, self.eng.stream)
-                self._packed[key] = dst
-            d.wt = _ptr(self._packed[key])
-            L.call("csbsr_conv_x3w_forward", C.byref(d), self.eng.stream)
-        elif x3 is not None and self.eng.use_x3 and L.load().csbsr_conv_x3_eligible(C.byref(d)):
-            # wide low-resolution 3x3 layers (SFT convs and their dgrads): per-chunk halo tile + fragment-ordered weights from L2 (csrc/conv_x3.hip)
-            # ... and the k = 2 x stride strided layers (kind 2: 8x8 stride-4 convs, dgrads of the 8x8 stride-4 deconvs): chunk = input phase
-            kind, c_real, rows_real, row_off, k_off = x3
-            key = ("x3", kind, row_off, k_off, c_real)
-            if key not in self._packed:
-                if kind == 2:
-                    n = L.load().csbsr_packed_weight_elems_x3_strided(stride, c_real, rows_real)
-                    dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-                    L.call("csbsr_pack_weights_x3_strided", _ptr(self._wq()), _ptr(dst), self.w.shape[0], self.w.shape[1], k, stride, c_real,
-                           rows_real, row_off, k_off, self.eng.stream)
-                else:
-                    n = L.load().csbsr_packed_weight_elems_x3(c_real, rows_real)
-                    dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-                    L.call("csbsr_pack_weights_x3", _ptr(self._wq()), _ptr(dst), kind, self.w.shape[0], self.w.shape[1], c_real, rows_real, row_off,
-                           k_off, self.eng.stream)
-                self._packed[key] = dst
-            d.wt = _ptr(self._packed[key])
-            L.call("csbsr_conv_x3_forward", C.byref(d), self.eng.stream)
-        elif use_tp and L.load().csbsr_conv_tp_eligible(C.byref(d)):
-            # 2x2-tap transposed layers (8x8 stride 4 / 12x12 stride 8): resident halo tile + streamed fragment-ordered weights (csrc/conv_tp.hip)
-            c_real, rows_real, row_off, k_off = tp
-            key = ("tp", row_off, k_off)
-            if key not in self._packed:
-                n = L.load().csbsr_packed_weight_elems_tp(stride, c_real)
-                dst = torch.empty(n, dtype=torch.float16, device=self.eng.device)
-                L.call("csbsr_pack_weights_tp", _ptr(self._wq()), _ptr(dst), self.w.shape[0], self.w.shape[1], k, k, stride, pad, c_real, rows_real,
-                       row_off, k_off, self.eng.stream)
-                self._packed[key] = dst
-            d.wt = _ptr(self._packed[key])
-            L.call("csbsr_conv_tp_forward", C.byref(d), self.eng.stream)
-        else:
-            L.call("csbsr_conv_forward", C.byref(d), self.eng.stream)
-        if tm is not None:
-            ev1.record()
+                d.mask_slope = float(mslope)
+        if x0.lo and plan in (4, 5) and not lib.csbsr_conv_split_fused_eligible(C.byref(d)):     # the fused split stage is refused
+            if plan == 4:
+                d.inp[1] = x0.split_segs()[1]
+            d.split_fused, d.wt, plan = 0, _ptr(fallback()), (3 if plan == 4 else 2)
+        # ---- dispatch: the first family of the table that is offered this launch, switched on and eligible
+        facts = (op, sp, hp, transposed, len(xs), None if stat is None else stat_mode, dact is not None, cb_mode, plan, bool(x0.lo))
+        route = self._routes.get(facts)
+        if route is None:               # (the gates are pure functions of these facts and of what the layer fixed at construction)
+            route = self._routes[facts] = tuple(fam for fam in FAMILIES if op in fam.gates and fam.gates[op](self, Launch(*facts)))
+        self.last_fused, no_tp = (False, False) if dact is None else self._fill_dact(d, lib, TP in route, dact, dres)
+        t0 = eng.tic()
+        symbol, ref, asked = "csbsr_conv_forward", C.byref(d), {}
+        for fam in route:
+            if not fam.on(eng, self) or (no_tp and fam is TP):
+                continue
+            ans = asked.get(fam.eligible)           # (conv_x3n stands at two places: asked once)
+            if ans is None:
+                ans = asked[fam.eligible] = getattr(lib, fam.eligible)(ref)
+            if ans >= fam.accept:
+                key = fam.key(blk, x0)
+                dst = self._packed.get(key)
+                d.wt = _ptr(dst if dst is not None else self._pack_new(key, self._wq(), *fam.operand(self, blk, x0, pad)))
+                symbol = fam.forward
+                break
+        L.call(symbol, ref, eng.stream)
+        if t0 is not None:
             # algorithmic work of the layer: ONE product per (pixel, cout, cin, tap).  The split-precision launches execute more --
             # three K blocks for a hi+lo input against hi+lo weights, two for a gradient against hi+lo weights (the same tensor passed
             # twice) -- which goes into the last field, not into the FLOPs
+            k, stride = self.k, self.stride
             twice = len(xs) == 2 and xs[0] is xs[1]
             ctot = xs[0].c if twice else sum(f.c for f in xs)
-            executed = (2 if split_blocks in (2, 5) else 3) if x0.lo else (2 if twice else 1)
+            executed = (2 if plan in (2, 5) else 3) if x0.lo else (2 if twice else 1)
             npx = x0.N * OH * OW
             taps = k * k if not transposed else ((k + stride - 1) // stride) ** 2
             flops = 2.0 * npx * cout * ctot * taps
@@ -644,8 +651,8 @@ class Conv:
             nepi = sum(1 for f in (res, res2) if f is not None and not f.bcast) + int(bool(accumulate)) + int(mask is not None or dact is not None) + int(dres is not None)
             nbytes = 2.0 * (sum(0 if f.bcast else f.N * f.H * f.W * f.c for f in (xs[:1] if twice else xs)) + (npx * cout if out is not None else 0)
                             + nepi * npx * cout)
-            tm.append(("conv", flops, nbytes, ev0, ev1, self.name, (x0.N, H, W, ctot, cout, k, stride, int(transposed)),
-                       int(L.load().csbsr_debug_last_conv_kernel()), executed))
+            eng.toc(t0, "conv", flops, nbytes, self.name, (x0.N, x0.H, x0.W, ctot, cout, k, stride, int(transposed)),
+                    int(lib.csbsr_debug_last_conv_kernel()), executed)
 
     def fwd(self, x, out=None, out32=None, res=None, res2=None, res_mode=L.RES_NONE, stat=None, stat_mode=L.STAT_NONE, store=True):
         xs = x if isinstance(x, (tuple, list)) else (x,)
@@ -656,41 +663,31 @@ class Conv:
         if self._head1_ok(xs, out, out32, res, stat):
             # 1-channel head (PSPNet's ``final`` / aux classifier): fp32 VALU dot product over the pixel's channels, one streaming pass
             # (csbsr_head1_fwd) instead of a 32-row MFMA tile for one output channel; the split planes are summed, the weights not rounded
+            # (the weight row [1, C, 1, 1] as a contiguous fp32 vector: a view of the master weights)
             f = xs[0]
-            tm = self.eng.timing
-            if tm is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            L.call("csbsr_head1_fwd", _ptr(f.t), f.ld, f.lo, f.cp, _ptr(self._head1_w()), _ptr(self.b), int(self.act == L.ACT_SIGMOID),
+            t0 = self.eng.tic()
+            L.call("csbsr_head1_fwd", _ptr(f.t), f.ld, f.lo, f.cp, _ptr(self.w.reshape(-1)), _ptr(self.b), int(self.act == L.ACT_SIGMOID),
                    _ptr(out32), f.npix, self.eng.stream)
-            if tm is not None:
-                ev1.record()
-                tm.append(("conv", 2.0 * f.npix * f.c, 2.0 * f.npix * f.c * (2 if sp else 1) + 4.0 * f.npix, ev0, ev1, self.name,
-                           (f.N, H, W, f.c, 1, 1, 1, 0), 21, 1))
+            if t0 is not None:
+                self.eng.toc(t0, "conv", 2.0 * f.npix * f.c, 2.0 * f.npix * f.c * (2 if sp else 1) + 4.0 * f.npix, self.name,
+                             (f.N, H, W, f.c, 1, 1, 1, 0), HEAD1_FWD, 1)
             return None
         if out is None and store and out32 is None:
             out = self.eng.new(xs[0].N, OH, OW, self.cout, split=sp)
-        osc, nb = 1.0, 3
+        osc, nb, fb = 1.0, 3, None
         x_in = xs
         if sp:
             assert not self.transposed and self.split[1] == 0
-            xs, wt, osc, nb = self._split_operand(xs[0], "fwd_split", 0, self.cin, self.cout, self.stride, self.pad)
-        elif self.transposed:
-            wt = self._pack("fwd", 2, self.split[0], self.split[1], 0, self.cout, self.stride, self.pad)
+            xs, wt, osc, nb, fb = self._split_operand(xs[0], "fwd", 0, self.cin, self.cout, self.stride, self.pad)
         else:
-            wt = self._pack("fwd", 0, self.split[0], self.split[1], 0, self.cout, self.stride, self.pad)
-        hr = (0, self.cin, self.cout, 0) if (not sp and not self.transposed and self.k in (1, 3) and len(xs) == 1 and self.prelu is None) else None
+            wt = self._pack("fwd", 2 if self.transposed else 0, self.split[0], self.split[1], 0, self.cout, self.stride, self.pad)
         # (split inputs: only where the layer's plan keeps the weight's rounding, i.e. runs fewer than three products)
         bias = self._dc_bias(x_in) if (self.dc_comp and self.eng.dc_comp and not self.transposed and (not sp or self.fwd_blocks < 3)
                                        and (OH * OW) % 256 == 0 and self.cin > 8) else self.b
-        self._launch(xs, wt, self.transposed, self.k, self.stride, self.pad, self.dil, H, W, OH, OW, self.cout, out, out32, bias,
-                     self.act, self.slope, self.prelu, res, res2, res_mode, False, stat, stat_mode, osc, hr=hr,
-                     tp=(self.cin, self.cout, 0, 0) if (self.transposed and len(xs) == 1 and not sp) else None,
-                     x3=((0 if self.k == 3 else 2, self.cin, self.cout, 0, 0)
-                         if (not sp and not self.transposed and len(xs) == 1 and (self.k == 3 or self.k == 2 * self.stride)) else None),
-                     split_blocks=nb,
-                     x3n=(0, self.cin, self.cout, 0, 0) if (not self.transposed and len(xs) == 1 and self.k == 3 and self.stride == 1
-                                                           and (stat is None or stat_mode == L.STAT_BN)) else None)
+        # (kind 2: the k = 2 x stride layers of conv_x3; the other families take k = 1 / 3 or do not read it)
+        self._launch("fwd", xs, wt, WBlock(0 if self.k in (1, 3) else 2, self.cin, self.cout, 0, 0), self.transposed, self.pad, self.dil, OH, OW,
+                     out=out, out32=out32, bias=bias, epilogue=True, res=res, res2=res2, res_mode=res_mode, stat=stat, stat_mode=stat_mode,
+                     out_scale=osc, sp=sp, plan=nb, fallback=fb)
         return out
 
     def bwd_input(self, dpre, seg=0, out=None, accumulate=False, out32=None, stat=None, in_hw=None, mask=None, dact=None, dres=None):
@@ -711,50 +708,33 @@ class Conv:
             if out is None:
                 out = self.eng.new(dpre.N, H, W, c_seg)
             if out.flat_ok() and not out.lo:
-                tm = self.eng.timing
-                if tm is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                L.call("csbsr_head1_bwd_input", _ptr(dpre.t), dpre.ld, _ptr(self._head1_w()), c_seg, _ptr(out.t), out.ld, dpre.npix, self.eng.stream)
-                if tm is not None:
-                    ev1.record()
-                    tm.append(("conv", 2.0 * dpre.npix * c_seg, 2.0 * dpre.npix * (c_seg + 8), ev0, ev1, self.name,
-                               (dpre.N, H, W, 1, c_seg, 1, 1, 0), 22, 1))
+                t0 = self.eng.tic()
+                L.call("csbsr_head1_bwd_input", _ptr(dpre.t), dpre.ld, _ptr(self.w.reshape(-1)), c_seg, _ptr(out.t), out.ld, dpre.npix, self.eng.stream)
+                if t0 is not None:
+                    self.eng.toc(t0, "conv", 2.0 * dpre.npix * c_seg, 2.0 * dpre.npix * (c_seg + 8), self.name,
+                                 (dpre.N, H, W, 1, c_seg, 1, 1, 0), HEAD1_BWD_INPUT, 1)
                 return out
         hp = self.hp_dgrad and not dpre.bcast and not self.transposed
-        if hp:       # weights as fp16 hi + lo pairs against the (plain fp16) gradient passed twice
-            kind = 1 if s == 1 else 2
-            wt = self._pack_split(("dg_hp", seg), kind, self.cout, c_seg, s if kind == 2 else 1, p, layout=1, row_off=row_off)
-            if s == 1:
-                OH, OW = in_hw if in_hw else (H + 2 * (d * (k - 1) - p) - d * (k - 1), W + 2 * (d * (k - 1) - p) - d * (k - 1))
-                tr, ps, pp, dd = False, 1, d * (k - 1) - p, d
-            else:
-                assert d == 1 and in_hw is not None
-                OH, OW = in_hw
-                tr, ps, pp, dd = True, s, p, 1
-        elif self.transposed:                      # dgrad of a transposed conv = strided conv on dOut
-            wt = self._pack(("dg", seg), 0, self.cout, 0, row_off, c_seg, s, p)
+        if self.transposed:                      # dgrad of a transposed conv = strided conv on dOut
             OH, OW = in_hw if in_hw else ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1)
-            tr, ps, pp, dd = False, s, p, 1
+            pk, tr, pp, dd = 0, False, p, 1
         elif s == 1:                             # flipped kernel, pad' = d(k-1) - p
-            wt = self._pack(("dg", seg), 1, self.cout, 0, row_off, c_seg, 1, p)
             OH, OW = in_hw if in_hw else (H + 2 * (d * (k - 1) - p) - d * (k - 1), W + 2 * (d * (k - 1) - p) - d * (k - 1))
-            tr, ps, pp, dd = False, 1, d * (k - 1) - p, d
+            pk, tr, pp, dd = 1, False, d * (k - 1) - p, d
         else:                                    # strided conv: gather-form transposed conv on dOut
             assert d == 1 and in_hw is not None
-            wt = self._pack(("dg", seg), 2, self.cout, 0, row_off, c_seg, s, p)
             OH, OW = in_hw
-            tr, ps, pp, dd = True, s, p, 1
+            pk, tr, pp, dd = 2, True, p, 1
+        if hp:       # weights as fp16 hi + lo pairs against the (plain fp16) gradient passed twice
+            wt = self._pack_split(("dg_hp", seg), pk, self.cout, c_seg, s, p, layout=1, row_off=row_off)
+        else:
+            wt = self._pack(("dg", seg), pk, self.cout, 0, row_off, c_seg, s, p)
         if out is None and out32 is None and stat is None:
             out = self.eng.new(dpre.N, OH, OW, c_seg)
-        hr = (1, self.cout, c_seg, row_off) if (not hp and not self.transposed and s == 1 and k in (1, 3) and stat is None) else None
-        self._launch((dpre, dpre) if hp else (dpre,), wt, tr, k, ps, pp, dd, H, W, OH, OW, c_seg, out, out32, None, L.ACT_NONE, 0.0, None,
-                     None, None, L.RES_NONE, accumulate, stat, L.STAT_SAMPLE_SUM if stat is not None else L.STAT_NONE,
-                     1.0 / self.WSCALE if hp else 1.0, mask=mask, hr=hr,
-                     tp=(self.cout, c_seg, row_off, 0) if (tr and not hp and stat is None) else None, dact=dact, dres=dres,
-                     x3=((2, self.cout, c_seg, row_off, 0) if (self.transposed and not hp and stat is None and k == 2 * s) else
-                         (1, self.cout, c_seg, row_off, 0) if (not hp and not self.transposed and s == 1 and k == 3 and stat is None) else None),
-                     x3n=(1, self.cout, c_seg, row_off, 0) if (not hp and not self.transposed and s == 1 and k == 3 and stat is None and dact is None) else None)
+        self._launch("dgrad", (dpre, dpre) if hp else (dpre,), wt, WBlock(2 if (self.transposed or s > 1) else 1, self.cout, c_seg, row_off, 0),
+                     tr, pp, dd, OH, OW, out=out, out32=out32, accumulate=accumulate, stat=stat,
+                     stat_mode=L.STAT_SAMPLE_SUM if stat is not None else L.STAT_NONE, out_scale=1.0 / self.WSCALE if hp else 1.0,
+                     mask=mask, dact=dact, dres=dres, hp=hp)
         return out
 
     # -- exact folding of a spatially constant second input segment (SFT conv0: cat(features, kernel code), kbpn.py:513)
@@ -765,11 +745,7 @@ class Conv:
         cf = self.split[0]
         B = x.N
         sp = bool(x.lo)
-        xs, osc, nb = (x,), 1.0, 3
-        if sp:
-            xs, wt, osc, nb = self._split_operand(x, "fwd_feat_split", 0, cf, self.cout, 1, self.pad)
-        else:
-            wt = self._pack("fwd_feat", 0, cf, 0, 0, self.cout, 1, self.pad, 0)
+        xs, wt, osc, nb, fb = self._split_operand(x, "fwd_feat", 0, cf, self.cout, 1, self.pad)
         # the constant part is a tiny fp32 mat-vec on the fp32 master weights and the fp32 kernel code (rounds 1-3 rounded both to fp16 in the
         # plain mode "to mirror the MFMA path": a precision loss the reference does not have and the fold does not need)
         w16c = self.w[:, cf:]
@@ -782,9 +758,8 @@ class Conv:
         if out is None:
             out = self.eng.new(B, H, W, self.cout, split=sp)
         bias = self._dc_bias((x,)) if (self.dc_comp and self.eng.dc_comp and (not sp or self.fwd_blocks < 3) and (x.H * x.W) % 256 == 0) else self.b      # (the feature segment; the constant one is an fp32 mat-vec)
-        self._launch(xs, wt, False, 3, 1, self.pad, self.dil, H, W, H, W, self.cout, out, None, bias, self.act, self.slope, self.prelu,
-                     None, None, L.RES_NONE, False, None, L.STAT_NONE, osc, cbias=cb,
-                     x3=None if sp else (0, cf, self.cout, 0, 0), split_blocks=nb, x3n=(0, cf, self.cout, 0, 0))
+        self._launch("folded", xs, wt, WBlock(0, cf, self.cout, 0, 0), False, self.pad, self.dil, H, W, out=out, bias=bias, epilogue=True,
+                     out_scale=osc, cbias=cb, sp=sp, plan=nb, fallback=fb)
         return out, (w16c, k16)
 
     def fwd_classbias(self, x, cb, cb_mode, out=None):
@@ -796,9 +771,8 @@ class Conv:
         wt = self._pack("fwd_feat", 0, cf, 0, 0, self.cout, 1, self.pad, 0)
         if out is None:
             out = self.eng.new(x.N, x.H, x.W, self.cout)
-        self._launch((x,), wt, False, self.k, 1, self.pad, self.dil, x.H, x.W, x.H, x.W, self.cout, out, None, self.b, self.act, self.slope,
-                     self.prelu, None, None, L.RES_NONE, False, None, L.STAT_NONE, 1.0, cbias=cb, cb_mode=cb_mode,
-                     hr=(0, cf, self.cout, 0) if (self.k == 1 and cb_mode == 1 and self.prelu is None) else None)
+        self._launch("classbias", (x,), wt, WBlock(0, cf, self.cout, 0, 0), False, self.pad, self.dil, x.H, x.W, out=out, bias=self.b,
+                     epilogue=True, cbias=cb, cb_mode=cb_mode)
         return out
 
     def fwd_const_1x1(self, cvec, x, out=None, stat=None, stat_mode=L.STAT_NONE):
@@ -808,18 +782,14 @@ class Conv:
         c0 = self.split[0]
         B = x.N
         sp = bool(x.lo)
-        xs, osc, nb = (x,), 1.0, 3
-        if sp:
-            xs, wt, osc, nb = self._split_operand(x, "fwd_x_split", 0, self.split[1], self.cout, 1, 0, k_off=c0)
-        else:
-            wt = self._pack("fwd_x", 0, self.split[1], 0, 0, self.cout, 1, 0, c0)
+        xs, wt, osc, nb, fb = self._split_operand(x, "fwd_x", 0, self.split[1], self.cout, 1, 0, k_off=c0)
         T = cvec.to(torch.float32) @ self.w[:, :c0, 0, 0].t()              # [B, cout]
         cb = self.eng.f32(B, 16, pad8(self.cout))
         cb[:, :, :self.cout] = T[:, None, :]
         if out is None:
             out = self.eng.new(B, x.H, x.W, self.cout, split=sp)
-        self._launch(xs, wt, False, 1, 1, 0, 1, x.H, x.W, x.H, x.W, self.cout, out, None, self.b, self.act, self.slope, self.prelu,
-                     None, None, L.RES_NONE, False, stat, stat_mode, osc, cbias=cb, split_blocks=nb)
+        self._launch("const", xs, wt, WBlock(0, self.split[1], self.cout, 0, c0), False, 0, 1, x.H, x.W, out=out, bias=self.b, epilogue=True,
+                     stat=stat, stat_mode=stat_mode, out_scale=osc, cbias=cb, sp=sp, plan=nb, fallback=fb)
         return out
 
     def bwd_weights_folded(self, dpre, x, saved, mtap, frozen=False, bias_grad=False, prelu_out=None):
@@ -923,17 +893,13 @@ class Conv:
         splits = L.load().csbsr_wgrad_splits_desc(C.byref(d))
         g = self.eng.workspace(splits * a.cp * ktot)
         d.g, d.splits = _ptr(g), splits
-        tm = self.eng.timing
-        if tm is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        t0 = self.eng.tic()
         L.call("csbsr_conv_wgrad", C.byref(d), self.eng.stream)
-        if tm is not None:
-            ev1.record()
+        if t0 is not None:
             flops = 2.0 * a.N * a.H * a.W * a.c * sum(f.c for f in bs) * self.k * self.k
             nbytes = 2.0 * (a.N * a.H * a.W * a.c + sum(0 if f.bcast else f.N * f.H * f.W * f.c for f in bs))
-            tm.append(("wgrad", flops, nbytes, ev0, ev1, self.name, (a.N, a.H, a.W, a.c, sum(f.c for f in bs), self.k, self.stride, int(self.transposed)),
-                       int(L.load().csbsr_debug_last_wgrad_kernel())))
+            self.eng.toc(t0, "wgrad", flops, nbytes, self.name, (a.N, a.H, a.W, a.c, sum(f.c for f in bs), self.k, self.stride, int(self.transposed)),
+                         int(L.load().csbsr_debug_last_wgrad_kernel()))
         gacc = grad_acc(self.w)
         L.call("csbsr_unpack_wgrad", _ptr(g), C.c_void_p(gacc.data_ptr() + 4 * a_off * self.k * self.k), A_real, self.k, self.k, seg0, seg1,
                self.w.shape[0], self.w.shape[1], unpack_mode, 0, 1.0, splits, a.cp, self.eng.stream)

@@ -6,6 +6,7 @@ import re
 _CONV = {0: "conv_igemm_kernel<32,4,1>", 1: "conv_igemm_kernel<64,2,2>", 2: "conv_igemm_kernel<128,2,2>", 5: "conv_thin_cout_kernel",
          6: "conv_thin_cin_kernel", 11: "conv_thin_tp_kernel", 13: "conv_thin_cin2_kernel", 15: "conv_thin_sc_kernel", 16: "conv_thin_tpd_kernel",
          10: "conv_x3_kernel<3>", 12: "conv_x3_kernel<2>", 17: "conv_x3_kernel<3,1024>", 18: "conv_x3_kernel<2,1024>"}
+HEAD1_FWD, HEAD1_BWD_INPUT = 21, 22         # the 1-channel heads (csbsr_head1_fwd / csbsr_head1_bwd_input): ids the engine gives them itself
 _GLDS = {3: (128, 2, 2, 1), 4: (256, 4, 3, 1), 7: (256, 4, 2, 2), 14: (128, 2, 2, 0)}
 _WGRAD = {0: "conv_wgrad_kernel<128,128,2,2>", 1: "conv_wgrad_kernel<128,256,2,4>", 2: "conv_wgrad_kernel<64,128,2,2>",
           3: "conv_wgrad_kernel<32,128,1,4>", 4: "conv_wgrad_thin_kernel", 5: "conv_wgrad_glds_kernel<128,128>",
@@ -28,8 +29,8 @@ def conv_row(kid):
         return "conv_x3_kernel<3,2048>"
     if base == 19:
         return f"conv_x3w_kernel<{var}>"
-    if base in (21, 22):
-        return "head1_fwd_kernel" if base == 21 else "head1_bwd_input_kernel"
+    if base in (HEAD1_FWD, HEAD1_BWD_INPUT):
+        return "head1_fwd_kernel" if base == HEAD1_FWD else "head1_bwd_input_kernel"
     if base == 20:
         return "conv_x3n_kernel<%d,%d%s%s>" % (var & 1, (var >> 1) & 1, ",wide" if var & 4 else "", ",lean" if var & 8 else "")
     return _CONV.get(base, f"conv?{base}")

@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from csbsr_amd import _lib as L
-from csbsr_amd.engine import Engine, Conv, FM, pad8
+from csbsr_amd.engine import Engine, Conv, FM, WBlock, pad8
 
 def run(name, N, H, W, cin, cout, k, s, p, d=1, tr=False, iters=10, what=("fwd", "fwd_noepi")):
     eng = Engine()
@@ -22,7 +22,7 @@ def run(name, N, H, W, cin, cout, k, s, p, d=1, tr=False, iters=10, what=("fwd",
     if tr: flops = 2.0 * N * OH * OW * cout * cin * taps
     res = {}
     for w_ in what:
-        fn = {"fwd": lambda: conv.fwd(x, out=y), "fwd_noepi": lambda: conv._launch((x,), conv._pack("fwd", 2 if tr else 0, cin, 0, 0, cout, s, p), tr, k, s, p, d, H, W, OH, OW, cout, y, None, None, 0, 0.0, None, None, None, 0, False, None, 0, -12345.0), "dgrad": lambda: conv.bwd_input(dy, out=dx, in_hw=(H, W)), "wgrad": lambda: conv.bwd_weights(dy, x)}[w_]
+        fn = {"fwd": lambda: conv.fwd(x, out=y), "fwd_noepi": lambda: conv._launch(None, (x,), conv._pack("fwd", 2 if tr else 0, cin, 0, 0, cout, s, p), WBlock(0, cin, cout, 0, 0), tr, p, d, OH, OW, out=y, out_scale=-12345.0), "dgrad": lambda: conv.bwd_input(dy, out=dx, in_hw=(H, W)), "wgrad": lambda: conv.bwd_weights(dy, x)}[w_]
         fn(); torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
