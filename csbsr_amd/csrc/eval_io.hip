@@ -4,13 +4,16 @@
 //   csbsr_stitch_clip_u8        JointPatch (model/data/samplers/patch_sampler.py:30-51) + the two masked clip assignments of
 //                               model/engine/inference.py:94-95 + ToPILImage's mul(255).byte() and its CHW -> HWC, in one pass over the
 //                               model's patch batch: the stitched fp32 image for the metrics and / or the interleaved uint8 image for PIL.
+//   csbsr_stitch_tiles_u8       the ragged counterpart for images of any size (csbsr_amd/inference.py: predict_dataset): every patch carries a
+//                               table row that says which of its rectangles goes where in which image of an output pool.
 //   csbsr_threshold_planes_u8   (pred - t_s > 0) * 255 for up to 16 thresholds (inference.py:111-118): one read of the map, S byte planes.
 //
-// Both are streaming kernels without LDS or scratch.  A lane owns a run of consecutive output pixels of one row -- 4 in the stitch
+// All are streaming kernels without LDS or scratch.  A lane owns a run of consecutive output pixels of one row -- 4 in the stitch
 // (a 16-byte load and store per fp32 plane, one 12-byte store of 4 RGB pixels or one dword of 4 grey ones), 16 in the threshold planes
 // (four 16-byte loads, one 16-byte store per plane) -- and a run never crosses a patch's right edge because the vector kernels run only
 // when pw % 4 == 0 (hw % 16 == 0) and every base is aligned; everything else takes the per-pixel kernels.  Every index is derived from
-// the arguments: a lane past the last run returns before it forms an address.
+// the arguments: a lane past the last run returns before it forms an address.  (The ragged stitch decides load, fp32 store and byte store
+// per lane at run time from the row's offsets, which are uniform per workgroup.)
 #include "common.h"
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -118,6 +121,113 @@ extern "C" int csbsr_stitch_clip_u8(const float* patches, int32_t B, int32_t C, 
   else        { if (vec) STITCH_LAUNCH(1, true); else STITCH_LAUNCH(1, false); }
 #undef STITCH_LAUNCH
   CSBSR_LAUNCH_CHECK("csbsr_stitch_clip_u8");
+  return 0;
+}
+
+// One workgroup row (blockIdx.y) per patch; a lane owns pixels x .. x + 3 of row y of the patch's owned rectangle.  The row of the table is
+// not trusted: the rectangle is cut to what lies inside the patch AND inside the image before any address is formed, so no read leaves patch
+// n and no write leaves the C * H * W elements of image `img`.  (img itself indexes dims / offsets as given, as in resident.hip.)
+// al: bit 0 = patches 16-byte aligned and PW % 4 == 0, bit 1 = out_f32 16-byte aligned, bit 2 = out_u8 4-byte aligned.
+template <int C>
+__global__ __launch_bounds__(256) void stitch_tiles_u8_kernel(const float* __restrict__ patches, int PH, int PW, int wq,
+                                                              const int32_t* __restrict__ tiles, const int64_t* __restrict__ offsets,
+                                                              const int32_t* __restrict__ dims, int clip, int al,
+                                                              float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
+  const int n = blockIdx.y;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= PH * wq) return;
+  const int y = idx / wq, x = (idx - y * wq) * 4;
+  const int32_t* t = tiles + (int64_t)n * 8;                       // uniform per workgroup
+  const int img = t[0];
+  const int H = dims[2 * img], W = dims[2 * img + 1];
+  if (H <= 0 || W <= 0) return;
+  const int dy = min(max(t[1], 0), H), dx = min(max(t[2], 0), W);
+  const int sy = min(max(t[3], 0), PH), sx = min(max(t[4], 0), PW);
+  const int th = min(min(t[5], PH - sy), H - dy), tw = min(min(t[6], PW - sx), W - dx);      // <= 0: nothing of this tile survives
+  if (y >= th || x >= tw) return;
+  const int m = min(4, tw - x);                                    // pixels of this lane
+  const int64_t plane = (int64_t)PH * PW, off = offsets[img], hw = (int64_t)H * W;
+  const float* src = patches + (int64_t)n * C * plane + (int64_t)(sy + y) * PW + sx + x;
+  float v[C][4];
+  if (m == 4 && (al & 1) && (sx & 3) == 0) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const f4 r = *reinterpret_cast<const f4*>(src + c * plane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[c][j] = r[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int xj = min(j, m - 1);                                // (a lane of the row tail re-reads its last pixel and does not store it)
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c][j] = src[c * plane + xj];
+    }
+  }
+  const int64_t pix = (int64_t)(dy + y) * W + dx + x;              // first pixel of the run inside its image
+  const bool run4 = m == 4 && ((W | dx) & 3) == 0 && (off & 3) == 0;      // pix % 4 == 0 and the image starts at a multiple of 4 elements
+  if (out_f32) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float* o = out_f32 + off + c * hw + pix;
+      f4 r;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = clip ? clip01_keep(v[c][j]) : v[c][j];
+      if (run4 && (al & 2)) {
+        *reinterpret_cast<f4*>(o) = r;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < m) o[j] = r[j];
+      }
+    }
+  }
+  if (out_u8) {
+    uint8_t* o = out_u8 + off + pix * C;
+    if (run4 && (al & 4)) {
+      uint32_t u[C] = {};                                          // byte k = j * C + c of the run: pixel j, channel c
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const int k = j * C + c;
+          u[k >> 2] |= quant_u8(v[c][j]) << (8 * (k & 3));
+        }
+      }
+      uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+      for (int c = 0; c < C; ++c) o32[c] = u[c];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < m) {
+#pragma unroll
+          for (int c = 0; c < C; ++c) o[j * C + c] = (uint8_t)quant_u8(v[c][j]);
+        }
+      }
+    }
+  }
+}
+
+extern "C" int csbsr_stitch_tiles_u8(const float* patches, int32_t N, int32_t C, int32_t PH, int32_t PW, const int32_t* tiles,
+                                     const int64_t* offsets, const int32_t* dims, int32_t clip, float* out_f32, uint8_t* out_u8,
+                                     csbsr_stream_t s) {
+  CSBSR_CHECK(patches && tiles && offsets && dims && (out_f32 || out_u8), "stitch_tiles_u8: null pointer (an input, or both outputs)");
+  CSBSR_CHECK(C == 1 || C == 3, "stitch_tiles_u8: C must be 1 or 3 (got %d)", C);
+  CSBSR_CHECK(N > 0 && PH > 0 && PW > 0, "stitch_tiles_u8: bad patch count / patch size");
+  const int wq = (PW + 3) / 4;
+  CSBSR_CHECK((int64_t)PH * wq < (1ll << 31) - 256, "stitch_tiles_u8: patch too large");
+  const int al = (((PW & 3) == 0 && (reinterpret_cast<uintptr_t>(patches) & 15) == 0) ? 1 : 0) |
+                 ((reinterpret_cast<uintptr_t>(out_f32) & 15) == 0 ? 2 : 0) | ((reinterpret_cast<uintptr_t>(out_u8) & 3) == 0 ? 4 : 0);
+  const int64_t plane = (int64_t)PH * PW;
+  for (int32_t n0 = 0; n0 < N; n0 += 65535) {                      // (grid.y carries the patch)
+    const dim3 grid(cdiv((int64_t)PH * wq, 256), min(N - n0, 65535)), block(256);
+    const float* p = patches + (int64_t)n0 * C * plane;            // (a multiple of 16 bytes whenever bit 0 of al is set)
+    const int32_t* t = tiles + (int64_t)n0 * 8;
+    if (C == 3) hipLaunchKernelGGL((stitch_tiles_u8_kernel<3>), grid, block, 0, ST(s), p, PH, PW, wq, t, offsets, dims, clip, al, out_f32, out_u8);
+    else        hipLaunchKernelGGL((stitch_tiles_u8_kernel<1>), grid, block, 0, ST(s), p, PH, PW, wq, t, offsets, dims, clip, al, out_f32, out_u8);
+  }
+  CSBSR_LAUNCH_CHECK("csbsr_stitch_tiles_u8");
   return 0;
 }
 

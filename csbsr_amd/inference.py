@@ -2,7 +2,9 @@
 (model/engine/inference.py:76-119) for one batch of test images -- patches through JointModel, stitch, clip, PSNR / SSIM of the SR
 image, PSNR of the kernel, and the IoU of the segmentation map at every threshold 0.01 .. 0.99 -- without the [B,99,H,W] broadcast
 tensor and the host numpy reductions.  ``evaluate_dataset`` runs it over a whole HBM-resident test set (csbsr_amd/data/resident_test.py) and
-returns the reference's final report, with the saved images and masks leaving the device as uint8 (csrc/eval_io.hip)."""
+returns the reference's final report, with the saved images and masks leaving the device as uint8 (csrc/eval_io.hip).
+``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
+of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device."""
 import csv
 import ctypes as C
 import os
@@ -75,6 +77,29 @@ def stitch_clip_u8(patches, unfold_shape, clip, want_f32=True, want_u8=False):
     return f32, u8
 
 
+def stitch_tiles_u8(patches, tiles, offsets, dims, clip, out_f32=None, out_u8=None):
+    """csbsr_stitch_tiles_u8: the owned rectangle of every patch of fp32 ``patches`` [N, C, PH, PW] into the output pools, in place, by the
+    int32 device table ``tiles`` [N, 8] = (image, dst_y, dst_x, src_y, src_x, th, tw, 0) over the int64 ``offsets`` [n] and int32 ``dims``
+    [n, 2] tables of the output images (include/csbsr_hip.h).  ``out_f32``: flat fp32 pool, planar per image; ``out_u8``: flat uint8 pool,
+    interleaved per image; at least one.  The caller sizes the pools for the tables and keeps the image column inside them."""
+    if not patches.is_cuda:
+        raise L.CsbsrHipError("stitch_tiles_u8 needs the patches on a GPU: csbsr_amd has no fallback path")
+    if out_f32 is None and out_u8 is None:
+        raise L.CsbsrHipError("stitch_tiles_u8: no output pool")
+    p = patches.to(torch.float32).contiguous()
+    if p.dim() != 4 or tuple(tiles.shape) != (p.shape[0], 8) or tiles.dtype != torch.int32 or not tiles.is_contiguous():
+        raise ValueError(f"patches {tuple(patches.shape)} need one contiguous int32 row of 8 each: tiles {tuple(tiles.shape)} {tiles.dtype}")
+    if offsets.dtype != torch.int64 or dims.dtype != torch.int32 or dims.shape != (offsets.numel(), 2) or not dims.is_contiguous():
+        raise ValueError("offsets must be int64 [n] and dims contiguous int32 [n, 2]")
+    for o, dt in ((out_f32, torch.float32), (out_u8, torch.uint8)):
+        if o is not None and (o.dtype != dt or not o.is_contiguous() or o.device != p.device):
+            raise ValueError(f"an output pool must be a contiguous {dt} tensor on {p.device}")
+    N, Cc, PH, PW = p.shape
+    with torch.cuda.device(p.device):
+        L.call("csbsr_stitch_tiles_u8", _ptr(p), N, Cc, PH, PW, _ptr(tiles), _ptr(offsets), _ptr(dims), int(bool(clip)),
+               None if out_f32 is None else _ptr(out_f32), None if out_u8 is None else _ptr(out_u8), _stream(p))
+
+
 def threshold_planes_u8(pred, thresholds32):
     """csbsr_threshold_planes_u8: uint8 [N, S, *pred.shape[1:]] = 255 where pred - t_s > 0 (fp32), for fp32 device tensors pred [N, ...] and
     thresholds32 [S], 1 <= S <= 16."""
@@ -138,7 +163,11 @@ def classification_scores(counts):
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
-    encodes with PIL -- the caller drains batch k after it has enqueued batch k + 1."""
+    encodes with PIL -- the caller drains batch k after it has enqueued batch k + 1.
+
+    A batch is (img [B,H,W,3], raw [B,H,W,1], planes [B,S,H,W], kern [B * nP,1,K,K]) of equal images, or, with ``layout`` = one
+    (pixel offset, H, W, first kernel, kernels) per image, flat pools of images of any size: img [3 * npix] interleaved per image, raw [npix],
+    planes [1,S,npix], kern [sum of kernels,1,K,K]."""
 
     def __init__(self, save_dir, thresholds):
         self.dir = save_dir
@@ -147,7 +176,7 @@ class _Saver:
             os.makedirs(os.path.join(save_dir, d), exist_ok=True)
         self.ring, self.n, self.pending = [None] * _SLOTS, 0, []
 
-    def push(self, fnames, tensors):
+    def push(self, fnames, tensors, layout=None):
         """tensors: device tensors of any dtype; their bytes go back to back into the slot's pinned buffer."""
         need = sum(-(-t.numel() * t.element_size() // 16) * 16 for t in tensors)          # every view starts at a multiple of 16
         slot = self.ring[self.n % _SLOTS]
@@ -163,23 +192,29 @@ class _Saver:
             views.append(v)
             off += -(-nb // 16) * 16
         ev.record(torch.cuda.current_stream(tensors[0].device))
-        self.pending.append((fnames, views, ev))
+        self.pending.append((fnames, views, ev, layout))
 
     def drain(self, keep=0):
         from PIL import Image
         while len(self.pending) > keep:
-            fnames, (img, raw, planes, kern), ev = self.pending.pop(0)
+            fnames, (img, raw, planes, kern), ev, layout = self.pending.pop(0)
             ev.synchronize()                                 # this slot's copies only
             img, raw, planes = img.numpy(), raw.numpy(), planes.numpy()
             nP = kern.shape[0] // len(fnames)
             for b, name in enumerate(fnames):
-                Image.fromarray(img[b]).save(os.path.join(self.dir, "images", name))
+                if layout is None:
+                    img_b, raw_b, planes_b, k0 = img[b], raw[b, :, :, 0], planes[b], b * nP
+                else:
+                    o, H, W, k0, nP = layout[b]
+                    img_b, raw_b = img[3 * o:3 * (o + H * W)].reshape(H, W, 3), raw[o:o + H * W].reshape(H, W)
+                    planes_b = planes[0, :, o:o + H * W].reshape(-1, H, W)
+                Image.fromarray(img_b).save(os.path.join(self.dir, "images", name))
                 for j, t in enumerate(self.th_names[:-1]):
-                    Image.fromarray(planes[b, j]).save(os.path.join(self.dir, "masks", t, name))
-                Image.fromarray(raw[b, :, :, 0]).save(os.path.join(self.dir, "masks", "th_-1.00", name))
+                    Image.fromarray(planes_b[j]).save(os.path.join(self.dir, "masks", t, name))
+                Image.fromarray(raw_b).save(os.path.join(self.dir, "masks", "th_-1.00", name))
                 stem = name.replace(".png", "")
                 for j in range(nP):                          # save_kernel: 441 values per patch, on the host
-                    k = kern[b * nP + j]
+                    k = kern[k0 + j]
                     for sub, tail, q in (("kernels", "", k / torch.max(k)), ("kernels_origin", "_origin", k / torch.sum(k))):
                         q8 = torch.nan_to_num(q, nan=0.0).mul(255).byte().numpy()[0]
                         Image.fromarray(q8).save(os.path.join(self.dir, sub, f"{stem}_{j}{tail}.png"))
@@ -253,3 +288,53 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
     if save_dir is not None:
         write_iou_log(os.path.join(save_dir, "iou_log.csv"), out["iou"], thresholds, fnames)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ prediction without ground truth
+@torch.no_grad()
+def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None):
+    """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
+    ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
+    csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
+    input pixel gets an output, and with the loader's ``halo`` every tile is convolved with real context instead of zero padding.
+
+    A GENERATOR: per image, in the set's order, it yields dict(name, sr_u8 [H,W,3] uint8, map_u8 [H,W] uint8, map_f32 [H,W] fp32,
+    kernels [tiles,1,K,K] fp32 clamped to [0, 1]) -- device tensors, views of the pools of the image's work unit.  The pools of one unit
+    are allocated when the unit starts and belong to whoever keeps the yielded tensors; the driver itself holds one unit at a time.
+
+    ``save_dir`` writes what ``evaluate_dataset`` writes, minus iou_log.csv -- images/<name>, masks/th_<t:.2f>/<name> for the threshold
+    indices [0, 9, 19, ..., 89, 98] (one csbsr_threshold_planes_u8 launch over the unit's flat map pool), masks/th_-1.00/<name>,
+    kernels/<stem>_<j>.png and kernels_origin/<stem>_<j>_origin.png, j over the image's tiles -- through the same ring of pinned slots; the
+    files of the last units are complete when the generator is exhausted."""
+    saver = _Saver(save_dir, thresholds) if save_dir is not None else None
+    th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
+    save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
+    s, dev = loader.scale, loader.device
+    want = (s * loader.wh, s * loader.ww)
+    for unit in loader:
+        sr_u8 = torch.empty(3 * unit.npix, dtype=torch.uint8, device=dev)
+        map_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
+        map_f32 = torch.empty(unit.npix, dtype=torch.float32, device=dev)
+        kernels = []
+        for imgs, a, b in loader.batches(unit):
+            dummy = torch.zeros((b - a, 1, ksize, ksize))
+            sr_p, seg_p, kernel_preds = model(imgs, dummy)
+            if tuple(sr_p.shape) != (b - a, 3, *want) or tuple(seg_p.shape) != (b - a, 1, *want):
+                raise ValueError(f"the model returned {tuple(sr_p.shape)} and {tuple(seg_p.shape)} for {b - a} windows of "
+                                 f"{loader.wh} x {loader.ww} at scale {s}: expected [n, 3 and 1, {want[0]}, {want[1]}]")
+            tiles = loader.stitch_dev[a:b]
+            stitch_tiles_u8(sr_p, tiles, loader.off3_dev, loader.out_dims_dev, clip=True, out_u8=sr_u8)
+            stitch_tiles_u8(seg_p, tiles, loader.off1_dev, loader.out_dims_dev, clip=False, out_f32=map_f32, out_u8=map_u8)
+            kernels.append(kernel_preds.clamp(0, 1).to(torch.float32))
+        kernels = torch.cat(kernels)
+        layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
+                   int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
+        if saver is not None:
+            planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
+            saver.push(loader.names[unit.i0:unit.i1], [sr_u8, map_u8, planes, kernels], layout=layout)
+            saver.drain(keep=1)                              # encode the unit before this one while the device runs this one
+        for i, (o, H, W, k0, nk) in zip(range(unit.i0, unit.i1), layout):
+            yield {"name": loader.names[i], "sr_u8": sr_u8[3 * o:3 * (o + H * W)].view(H, W, 3), "map_u8": map_u8[o:o + H * W].view(H, W),
+                   "map_f32": map_f32[o:o + H * W].view(H, W), "kernels": kernels[k0:k0 + nk]}
+    if saver is not None:
+        saver.drain()

@@ -512,6 +512,17 @@ int csbsr_gather_crop_u8(const uint8_t* pool, const int64_t* offsets, const int3
  * Either output may be NULL, not both. */
 int csbsr_stitch_clip_u8(const float* patches, int32_t B, int32_t C, int32_t nH, int32_t nW, int32_t ph, int32_t pw, int32_t clip,
                          float* out_f32, uint8_t* out_u8, csbsr_stream_t s);
+/* The ragged stitch for images of any size (csbsr_amd/inference.py: predict_dataset): patch n carries the row
+ *   tiles[n] = (image, dst_y, dst_x, src_y, src_x, th, tw, 0)     int32 [N][8], device memory, output pixels
+ * and for y < th, x < tw:   out[image][c][dst_y + y][dst_x + x] = patches[n][c][src_y + y][src_x + x],   values as in csbsr_stitch_clip_u8.
+ *   patches fp32 [N][C][PH][PW], C 1 or 3;  dims int32 [n_img][2] = (H, W) of the OUTPUT images;  offsets int64 [n_img]: the first element
+ *   of image i in either pool = C * (pixels of the images before it), the byte offsets of a uint8 pool of these images
+ *   out_f32: per image planar [C][H][W] at element offsets[i] (byte 4 * offsets[i]);  out_u8: per image H x W x C interleaved at byte offsets[i]
+ * Either output may be NULL, not both.  Pixels no tile owns are not written.  A row is not trusted: its rectangle is cut to the part inside
+ * the patch and inside the image, so no read leaves patches and no write leaves [offsets[i], offsets[i] + C * H * W) of its image; the
+ * image index is the caller's responsibility alone, as for csbsr_gather_crop_u8.  Tiles that overlap in the output race. */
+int csbsr_stitch_tiles_u8(const float* patches, int32_t N, int32_t C, int32_t PH, int32_t PW, const int32_t* tiles, const int64_t* offsets,
+                          const int32_t* dims, int32_t clip, float* out_f32, uint8_t* out_u8, csbsr_stream_t s);
 /* out[n][s][i] = (pred[n][i] - thresholds[s] > 0) ? 255 : 0, the subtraction in fp32 (the predicate of inference.py:111 and of
  * csbsr_iou_sweep), NaN -> 0.  pred fp32 [N][hw]; thresholds fp32 [S] device memory, 1 <= S <= 16, any order; out uint8 [N][S][hw]. */
 int csbsr_threshold_planes_u8(const float* pred, const float* thresholds, int32_t N, int64_t hw, int32_t S, uint8_t* out, csbsr_stream_t s);
