@@ -72,7 +72,7 @@ _C = CfgNode({
               "OPTIMIZER": "Adam", "UP_SAMPLE_METHOD": "deconv"},
     "SOLVER": {"MAX_ITER": 300000, "SR_PRETRAIN_ITER": [1, 30001], "SR_SR_MODULE_PRETRAIN_ITER": [1, 10001],
                "SR_KERNEL_MODULE_PRETRAIN_ITER": [10001, 20001], "ONLY_KERNEL_LOSS_FOR_PRETRAIN": False,
-               "SEG_PRETRAIN_ITER": [0, 0], "BATCH_SIZE": 8, "TASK_LOSS_WEIGHT": 0.3, "SEG_LOSS_FUNC": "BoundaryCombo",
+               "SEG_PRETRAIN_ITER": [0, 0], "INCRESE_TASK_W_ITER": [30000, 170000], "BATCH_SIZE": 8, "TASK_LOSS_WEIGHT": 0.3, "SEG_LOSS_FUNC": "BoundaryCombo",
                "BOUNDARY_DEC_RATIO": 1.0, "WB_AND_D_WEIGHT": [1, 1], "BCELOSS_WEIGHT": [1, 1], "SEG_AUX_LOSS_WEIGHT": 0.4,
                "SEG_MAIN_LOSS_WEIGHT": 1.0, "ORIENTED_WEIGHT_ITER": -1, "SEG_FAIL_ORIENTED_WEIGHT4SR_AMP": 0.0,
                "SEG_FAIL_ORIENTED_WEIGHT4SS_AMP": 0.0, "CRACK_ORIENTED_WEIGHT4SR_AMP": 0.0, "INTERM_SSLOSSWEGHT4SR": False,

@@ -314,6 +314,55 @@ extern "C" int csbsr_adam_step(const csbsr_adam_tensor_t* tensors, const int32_t
   CSBSR_LAUNCH_CHECK("csbsr_adam_step");
   return 0;
 }
+// ---- multi-tensor SGD (csbsr_hip.h): the chunk map and access pattern of the Adam kernel above; torch's foreach sequence per element
+// (d = g + wd p; buf = momentum buf + d; p -= lr buf).  A tensor whose p / g / buf is not 16-byte aligned (``vec`` = 0: a view that starts
+// inside an allocation) takes the scalar loop for the whole chunk.
+template <bool MOMENTUM, bool DECAY>
+__global__ __launch_bounds__(256) void sgd_step_kernel(const csbsr_sgd_tensor_t* __restrict__ tt, const int* __restrict__ bt,
+                                                       const int* __restrict__ bc, float lr, float momentum, float wd) {
+  const csbsr_sgd_tensor_t t = tt[bt[blockIdx.x]];
+  const long base = (long)bc[blockIdx.x] * ADAM_CHUNK;
+  const long rem = t.n - base;
+  const int cnt = rem < ADAM_CHUNK ? (int)rem : ADAM_CHUNK;
+  auto upd = [&](float& p, float g, float& b) {
+    float d = g;
+    if (DECAY) d = g + wd * p;
+    if (MOMENTUM) { b = momentum * b + d; d = b; }
+    p = p - lr * d;
+  };
+  const int nv = t.vec ? cnt >> 2 : 0;
+  float4* p4 = reinterpret_cast<float4*>(t.p + base);
+  const float4* g4 = reinterpret_cast<const float4*>(t.g + base);
+  float4* b4 = reinterpret_cast<float4*>(t.buf + base);      // (never dereferenced without MOMENTUM: buf may be NULL then)
+  for (int i = threadIdx.x; i < nv; i += 256) {
+    float4 p = p4[i], b = {0.f, 0.f, 0.f, 0.f};
+    const float4 g = g4[i];
+    if (MOMENTUM) b = b4[i];
+    upd(p.x, g.x, b.x); upd(p.y, g.y, b.y); upd(p.z, g.z, b.z); upd(p.w, g.w, b.w);
+    p4[i] = p;
+    if (MOMENTUM) b4[i] = b;
+  }
+  for (int i = 4 * nv + threadIdx.x; i < cnt; i += 256) {
+    float p = t.p[base + i], b = 0.f;
+    if (MOMENTUM) b = t.buf[base + i];
+    upd(p, t.g[base + i], b);
+    t.p[base + i] = p;
+    if (MOMENTUM) t.buf[base + i] = b;
+  }
+}
+extern "C" int csbsr_sgd_step(const csbsr_sgd_tensor_t* tensors, const int32_t* block_tensor, const int32_t* block_chunk, int32_t nblocks,
+                              double lr, double momentum, double weight_decay, csbsr_stream_t s) {
+  CSBSR_CHECK(tensors && block_tensor && block_chunk && nblocks >= 0, "sgd_step: bad arguments");
+  CSBSR_CHECK(momentum >= 0.0 && weight_decay >= 0.0, "sgd_step: momentum and weight_decay must not be negative");
+  if (nblocks == 0) return 0;
+  const bool mom = momentum != 0.0, dec = weight_decay != 0.0;
+  auto k = mom ? (dec ? sgd_step_kernel<true, true> : sgd_step_kernel<true, false>)
+               : (dec ? sgd_step_kernel<false, true> : sgd_step_kernel<false, false>);
+  hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), 0, reinterpret_cast<hipStream_t>(s), tensors, block_tensor, block_chunk, (float)lr,
+                     (float)momentum, (float)weight_decay);
+  CSBSR_LAUNCH_CHECK("csbsr_sgd_step");
+  return 0;
+}
 
 extern "C" int csbsr_axpby_split(int64_t npix, int32_t c, const void* x, int64_t x_ld, int64_t x_lo, float a, const void* z, int64_t z_ld,
                                  int64_t z_lo, float b, void* y, int64_t y_ld, int64_t y_lo, csbsr_stream_t s) {

@@ -226,7 +226,10 @@ class DeviceTrainLoader:
 
     Sampling (train.py:60-62): one permutation of the shard's samples per epoch, without replacement (RandomSampler); batches of
     ``batch_size``, the last of an epoch short unless ``drop_last`` (BatchSampler); epochs repeat until ``num_iterations`` batches have
-    been produced (IterationBasedBatchSampler), one epoch when it is None.  ``shard=(rank, world)`` keeps the samples at positions
+    been produced (IterationBasedBatchSampler), one epoch when it is None.  ``shuffle=False`` takes the shard's samples in dataset order
+    instead (SequentialSampler + BatchSampler, train.py:65-67: the validation loader); the crop, mirror and blur draws stay, as the
+    reference's validation split goes through the train transforms.  ``state_dict()`` / ``load_state_dict()`` carry the sequence over to
+    another loader (a resumed run).  ``shard=(rank, world)`` keeps the samples at positions
     ``i % world == rank`` of ``dataset``, so data-parallel ranks see disjoint data.
 
     Every draw comes from ONE seeded host ``torch.Generator`` (the blur parameters too: DeviceDegradation.draw_params is handed the same
@@ -246,7 +249,7 @@ class DeviceTrainLoader:
     """
 
     def __init__(self, dataset, crop, scale, ksize=21, *, batch_size, num_iterations=None, blur=True, isotropic=False, augmentation=None,
-                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1)):
+                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1), shuffle=True):
         self.dataset = dataset
         self.h, self.w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
         self.scale, self.K = int(scale), int(ksize)
@@ -255,7 +258,7 @@ class DeviceTrainLoader:
         self.batch_size, self.num_iterations = int(batch_size), None if num_iterations is None else int(num_iterations)
         if self.batch_size < 1:
             raise ValueError("batch_size must be positive")
-        self.blur, self.drop_last = bool(blur), bool(drop_last)
+        self.blur, self.drop_last, self.shuffle = bool(blur), bool(drop_last), bool(shuffle)
         self.vflip_p = float(vflip_p)
         if not 0.0 <= self.vflip_p <= 1.0:
             raise ValueError("vflip_p must be a probability")
@@ -277,7 +280,7 @@ class DeviceTrainLoader:
         self.deg = DeviceDegradation(self.scale, ksize=self.K, isotropic=isotropic, antialias=antialias, device=self.device)
         self.deg.gen = self.gen          # one generator for every draw
         self.antialias = bool(antialias)
-        self._perm, self._cursor = None, 0
+        self._perm, self._cursor, self._produced, self._resumed = None, 0, 0, False
         self._ring, self._slot = [None] * _SLOTS, 0
 
     @classmethod
@@ -296,7 +299,7 @@ class DeviceTrainLoader:
     def _next_indices(self, B):
         """The next <= B pool indices of the running epoch; a new permutation starts when the epoch is used up."""
         if self._perm is None or self._cursor >= len(self._perm):
-            self._perm = self.indices[torch.randperm(len(self.indices), generator=self.gen).numpy()]
+            self._perm = self.indices[torch.randperm(len(self.indices), generator=self.gen).numpy()] if self.shuffle else self.indices
             self._cursor = 0
         idx = self._perm[self._cursor:self._cursor + B]
         self._cursor += len(idx)
@@ -372,19 +375,47 @@ class DeviceTrainLoader:
         n = len(self.indices)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
+    @property
+    def produced(self):
+        """batches produced so far by the running (or loaded) sequence"""
+        return self._produced
+
     def iter_decisions(self):
         """The (sel, blur_params) sequence __iter__ turns into batches (host only)."""
-        self._perm, produced = None, 0
+        if self._resumed:          # a loaded state continues: same permutation, cursor and count (the generator was restored with them)
+            self._resumed = False
+            if self.num_iterations is None and self._perm is not None and self._cursor >= len(self._perm):
+                return             # (saved after the last batch of the single pass)
+        else:
+            self._perm, self._produced = None, 0
         if self.drop_last and len(self.indices) < self.batch_size:
             return
-        while self.num_iterations is None or produced < self.num_iterations:
+        while self.num_iterations is None or self._produced < self.num_iterations:
             sel, params = self.draw(self.batch_size)
             last = self._cursor >= len(self._perm)
             if not (self.drop_last and sel.shape[0] < self.batch_size):
-                produced += 1
+                self._produced += 1
                 yield sel, params
             if last and self.num_iterations is None:
                 return
+
+    def state_dict(self):
+        """What the decision sequence depends on, taken between two batches: the generator, the running epoch's permutation (pool
+        indices), the cursor in it and the number of batches produced.  Tensors and ints only."""
+        return {"generator": self.gen.get_state().clone(), "perm": None if self._perm is None else torch.from_numpy(np.array(self._perm)),
+                "cursor": int(self._cursor), "produced": int(self._produced), "samples": len(self.indices)}
+
+    def load_state_dict(self, state):
+        """Continue another loader's sequence: the next ``iter_decisions`` / ``__iter__`` of this loader goes on where that one stopped
+        instead of starting over.  The loader must have been built over the same shard with the same arguments."""
+        perm = state["perm"]
+        if int(state["samples"]) != len(self.indices) or (perm is not None and len(perm) != len(self.indices)):
+            raise ValueError(f"loader state of a shard of {int(state['samples'])} samples, this shard has {len(self.indices)}")
+        if perm is not None and not np.isin(np.asarray(perm), self.indices).all():
+            raise ValueError("loader state names samples outside this shard")
+        self.gen.set_state(torch.as_tensor(state["generator"], dtype=torch.uint8).cpu())
+        self._perm = None if perm is None else np.asarray(perm, dtype=np.int64).copy()
+        self._cursor, self._produced, self._resumed = int(state["cursor"]), int(state["produced"]), True
 
     def __iter__(self):
         for sel, params in self.iter_decisions():

@@ -8,6 +8,10 @@ work on it unchanged), the same per-parameter state keys (``step``, ``exp_avg``,
 ``torch.optim.Adam``), the same skip rule (a parameter whose ``.grad`` is None is not touched: no moment decay, no step count -- what the frozen
 training phases and an overflowed backward rely on), the same arithmetic operation by operation (agreement to fp32 rounding:
 tests/test_elementwise_gpu.py::test_adam_step_matches_torch).  fp32 parameters on the device only; anything else raises.
+
+``SGD`` is the same for ``torch.optim.SGD(params, lr, momentum=0.9, weight_decay=5e-4)`` (train.py:93, MODEL.OPTIMIZER "SGD"): one
+``csbsr_sgd_step`` launch per group over the same chunk map and staging table, torch's state key ``momentum_buffer``, torch's skip rule, and
+a ``state_dict()`` that ``torch.optim.SGD`` loads and steps from (tests/test_trainer_gpu.py::test_sgd_step_matches_torch).
 """
 import ctypes as C
 import math
@@ -20,16 +24,18 @@ from . import _lib as L
 _CHUNK = 8192
 _DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"), ("bc2_sqrt", "<f4")])
 assert _DT.itemsize == 48
+_SGD_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("vec", "<i4"), ("pad", "<i4")])
+assert _SGD_DT.itemsize == 40
 
 
-class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
+class _MultiTensor(torch.optim.Optimizer):
+    """What the one-launch optimisers share: the chunk map per set of tensor sizes and the pinned staging of the per-step table."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         L.load()
         self._maps = {}          # tuple of tensor sizes -> (block_tensor, block_chunk) device int32 tensors
-        self._host = None        # pinned staging for the per-step table (+ the event that says the last upload has been read)
+        self._host = {}          # group index -> pinned staging for its per-step table (+ the event that says the last upload has been read)
 
     def _block_maps(self, sizes, device):
         key = (tuple(sizes), str(device))
@@ -44,13 +50,45 @@ class Adam(torch.optim.Optimizer):
             self._maps[key] = mp
         return mp
 
+    def _launch(self, name, slot, tab, ps, dev, *scalars):
+        """Upload ``tab`` (one row per tensor of ``ps``, the stepped tensors of group ``slot``) and run entry point ``name`` over the chunk
+        map of ``ps`` on the current stream."""
+        bt, bc = self._block_maps([p.numel() for p in ps], dev)
+        raw = torch.from_numpy(tab.view(np.uint8))
+        host = self._host.get(slot)
+        if host is not None and host[0].numel() >= raw.numel() and host[1].device == dev:
+            host[2].synchronize()          # (the previous step's upload was consumed long ago: returns at once)
+        else:
+            n = max(raw.numel(), 4096)
+            host = self._host[slot] = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=dev),
+                                       torch.cuda.Event()]
+        host[0][:raw.numel()].copy_(raw)
+        with torch.cuda.device(dev):
+            host[1][:raw.numel()].copy_(host[0][:raw.numel()], non_blocking=True)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            L.call(name, C.c_void_p(host[1].data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(bc.data_ptr()), int(bt.numel()), *scalars, stream)
+            host[2].record(torch.cuda.current_stream(dev))
+
+
+def _check(p, g, dev, who):
+    if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and g.dtype == torch.float32 and not g.is_sparse
+            and g.is_contiguous() and g.device == p.device == dev):
+        raise L.CsbsrHipError(f"csbsr_amd.optim.{who}: contiguous fp32 parameters and gradients on one device only")
+
+
+class Adam(_MultiTensor):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("invalid Adam hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
+        for slot, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
@@ -60,30 +98,64 @@ class Adam(torch.optim.Optimizer):
             tab = np.zeros(len(ps), dtype=_DT)
             for i, p in enumerate(ps):
                 g = p.grad
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and g.dtype == torch.float32 and g.is_contiguous()
-                        and g.device == p.device == dev and not g.is_sparse):
-                    raise L.CsbsrHipError("csbsr_amd.optim.Adam: contiguous fp32 parameters and gradients on one device only")
+                _check(p, g, dev, "Adam")
                 st = self.state[p]
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                _check(p, st["exp_avg"], dev, "Adam")          # (a state_dict loaded while the parameters were still on the host)
+                _check(p, st["exp_avg_sq"], dev, "Adam")
                 st["step"] += 1
                 t = float(st["step"])
                 tab[i] = (p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
                           lr / (1.0 - beta1 ** t), math.sqrt(1.0 - beta2 ** t))
-            bt, bc = self._block_maps([p.numel() for p in ps], dev)
-            raw = torch.from_numpy(tab.view(np.uint8))
-            if self._host is not None and self._host[0].numel() >= raw.numel() and self._host[1].device == dev:
-                self._host[2].synchronize()          # (the previous step's upload was consumed long ago: returns at once)
-            else:
-                n = max(raw.numel(), 4096)
-                self._host = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=dev), torch.cuda.Event()]
-            self._host[0][:raw.numel()].copy_(raw)
-            with torch.cuda.device(dev):
-                self._host[1][:raw.numel()].copy_(self._host[0][:raw.numel()], non_blocking=True)
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                L.call("csbsr_adam_step", C.c_void_p(self._host[1].data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(bc.data_ptr()),
-                       int(bt.numel()), float(beta1), float(beta2), float(group["eps"]), stream)
-                self._host[2].record(torch.cuda.current_stream(dev))
+            self._launch("csbsr_adam_step", slot, tab, ps, dev, float(beta1), float(beta2), float(group["eps"]))
+        return loss
+
+
+class SGD(_MultiTensor):
+    """``torch.optim.SGD(params, lr, momentum, weight_decay=...)`` as one launch per group.  ``dampening``, ``nesterov`` and ``maximize`` are
+    accepted only at torch's defaults (they are carried in the group so that ``torch.optim.SGD`` can load this optimiser's state_dict and
+    step from it); any other value is a ValueError, at construction and again at a step that finds one loaded from a state_dict."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False):
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError("invalid SGD hyper-parameters")
+        self._refuse(dict(dampening=dampening, nesterov=nesterov, maximize=maximize))
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False, maximize=False,
+                                      foreach=None, differentiable=False, fused=None))
+
+    @staticmethod
+    def _refuse(group):
+        if group.get("nesterov") or group.get("dampening", 0) != 0 or group.get("maximize"):
+            raise ValueError("csbsr_amd.optim.SGD: nesterov, dampening != 0 and maximize are not built")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for slot, group in enumerate(self.param_groups):
+            self._refuse(group)
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            momentum = float(group["momentum"])
+            dev = ps[0].device
+            tab = np.zeros(len(ps), dtype=_SGD_DT)
+            for i, p in enumerate(ps):
+                g = p.grad
+                _check(p, g, dev, "SGD")
+                ptrs = [p.data_ptr(), g.data_ptr(), 0]
+                if momentum != 0:
+                    st = self.state[p]
+                    if st.get("momentum_buffer") is None:      # zeros: the kernel's first step then leaves buf = d, torch's clone
+                        st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    buf = st["momentum_buffer"]
+                    _check(p, buf, dev, "SGD")
+                    ptrs[2] = buf.data_ptr()
+                tab[i] = (*ptrs, p.numel(), int(all(a % 16 == 0 for a in ptrs)), 0)
+            self._launch("csbsr_sgd_step", slot, tab, ps, dev, float(group["lr"]), momentum, float(group["weight_decay"]))
         return loss

@@ -305,6 +305,19 @@ typedef struct {
 int csbsr_adam_step(const csbsr_adam_tensor_t* tensors, const int32_t* block_tensor, const int32_t* block_chunk, int32_t nblocks,
                     double beta1, double beta2, float eps, csbsr_stream_t s);
 
+/* SGD step (torch.optim.SGD without dampening / nesterov / maximize; train.py:93 uses momentum 0.9, weight_decay 5e-4) for a LIST of fp32
+ * tensors in one launch, with the chunk map of csbsr_adam_step: d = g + weight_decay p (skipped when weight_decay == 0); buf = momentum buf + d;
+ * p -= lr buf.  With momentum == 0 ``buf`` is not touched (it may be NULL) and p -= lr d.  A zero-filled ``buf`` makes the first step buf = d,
+ * which is what torch's clone of the first gradient gives.  ``vec`` != 0 states that p, g and buf are 16-byte aligned (float4 accesses); a
+ * tensor with vec == 0 is updated element by element. */
+typedef struct {
+  float* p; const float* g; float* buf;
+  int64_t n;
+  int32_t vec, _pad;
+} csbsr_sgd_tensor_t;
+int csbsr_sgd_step(const csbsr_sgd_tensor_t* tensors, const int32_t* block_tensor, const int32_t* block_chunk, int32_t nblocks,
+                   double lr, double momentum, double weight_decay, csbsr_stream_t s);
+
 int csbsr_axpby(int64_t npix, int32_t c, const void* x, int64_t x_ld, float a, const void* z, int64_t z_ld,
                 float b, void* y, int64_t y_ld, csbsr_stream_t s);
 int csbsr_fill_f16(void* p, int64_t npix, int32_t c, int64_t ld, float v, csbsr_stream_t s);
