@@ -156,7 +156,8 @@ SIGNATURES = {
     "csbsr_sigmoid_bwd_to_nhwc8": (i32, [vp, vp, vp, i64, f32, vp]),
     "csbsr_gaussian_kernels": (i32, [vp, vp, i32, i32, vp]),
     "csbsr_gather_crop_u8": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]),
-    "csbsr_stitch_clip_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "csbsr_gather_resize_u8": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp]),
+    "csbsr_stitch_clip_u8": (i32,[vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "csbsr_stitch_tiles_u8": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]),
     "csbsr_threshold_planes_u8": (i32, [vp, vp, i32, i64, i32, vp, vp]),
     "csbsr_iou_sweep": (i32, [vp, vp, vp, i32, i64, i32, f32, vp, vp, vp, vp, vp]),

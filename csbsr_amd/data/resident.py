@@ -8,7 +8,11 @@ device (10^4 images of 448^2 are 6 GB of pixels + 2 GB of masks), a batch is sel
 ``csbsr_amd.data.degrade.DeviceDegradation`` unchanged.  Per step the host contributes a table of 32 bytes per sample through a pinned
 staging buffer: no worker process, no pixel traffic over PCIe, no host float conversion, no wait for the batch's own device work.
 
-Kernels: csbsr_gather_crop_u8 (new) + those of DeviceDegradation.  No CPU / torch fallback: batches exist on a GPU only (the pool, the
+``resized_crop=`` (or a non-identity ``RandomResizedCrop`` entry of the augmentation list) turns the fixed-size window into the
+reference's RandomResizedCrop (transforms.py:607-622): a window of random area and aspect per sample, resampled to the crop size by
+``csbsr_gather_resize_u8`` in the same single launch per pool; the row per sample grows to 40 bytes.
+
+Kernels: csbsr_gather_crop_u8, csbsr_gather_resize_u8 + those of DeviceDegradation.  No CPU / torch fallback: batches exist on a GPU only (the pool, the
 sampler and the table validation also work on ``device="cpu"``, which is what the host-side tests use).
 """
 import ctypes as C
@@ -47,7 +51,8 @@ def interpret_augmentation(augmentation, crop, dims):
       RandomMirror                p = 0.5 (np.random.randint(2))
       RandomCrop                  a crop of INPUT.IMAGE_SIZE at a uniform offset; its resized_crop to the same size is the identity
       RandomResizedCrop           scale (1, 1), ratio (1, 1) only, and only when every image already has the crop size (then it is the
-                                  identity); anything else is NotImplementedError
+                                  identity); anything else is NotImplementedError HERE: DeviceTrainLoader takes a non-identity entry
+                                  out of the list itself (split_resized_crop) and hands this function a RandomCrop in its place
       any other entry with an argument (the yaml's ["RandomVerticalFlip", 0.3])
                                   the reference's ``else: eval(func)(args)`` constructs the transform and DROPS it: no effect there, none
                                   here.  Vertical flips are available through DeviceTrainLoader's explicit ``vflip_p``.
@@ -84,6 +89,40 @@ def interpret_augmentation(augmentation, crop, dims):
     if not out["crop"] and not all(int(H) == h and int(W) == w for H, W in dims):
         raise ValueError("the augmentation list has no crop, so every image must already have the crop size")
     return out
+
+
+def _resized_crop_args(rc):
+    """{"scale": (lo, hi), "ratio": (lo, hi)} with the reference's class defaults (transforms.py:608) -> ((lo, hi), (lo, hi)), validated."""
+    rc = dict(rc or {})
+    unknown = set(rc) - {"scale", "ratio"}
+    if unknown:
+        raise ValueError(f"resized_crop: unknown keys {sorted(unknown)}")
+    scale, ratio = tuple(float(v) for v in rc.get("scale", (0.5, 1.0))), tuple(float(v) for v in rc.get("ratio", (1.0, 1.0)))
+    if len(scale) != 2 or not 0.0 < scale[0] <= scale[1] or not np.isfinite(scale[1]):
+        raise ValueError(f"resized_crop: need 0 < scale_lo <= scale_hi, got {scale}")
+    if len(ratio) != 2 or not 0.0 < ratio[0] <= ratio[1] or not np.isfinite(ratio[1]):
+        raise ValueError(f"resized_crop: need 0 < ratio_lo <= ratio_hi, got {ratio}")
+    return scale, ratio
+
+
+def split_resized_crop(augmentation):
+    """(augmentation', resized_crop): a ``RandomResizedCrop`` entry that is not the identity case of interpret_augmentation (scale or
+    ratio other than (1, 1)) is replaced by ``("RandomCrop", None)`` -- so the ordering rules of interpret_augmentation still apply to
+    the place it stood in -- and its scale / ratio are returned; (augmentation, None) when there is no such entry."""
+    out, rc = [], None
+    for entry in augmentation:
+        func, args = entry
+        if func == "RandomResizedCrop":
+            kw = args[0] if isinstance(args, (list, tuple)) else args
+            kw = dict(kw or {}) if not _is_none(kw) else {}
+            scale, ratio = tuple(kw.get("scale", (0.5, 1.0))), tuple(kw.get("ratio", (1.0, 1.0)))
+            if scale != (1.0, 1.0) or ratio != (1.0, 1.0):
+                if rc is None:
+                    rc = {"scale": scale, "ratio": ratio}
+                out.append(("RandomCrop", None))          # (a second one is refused by interpret_augmentation: a crop after the crop)
+                continue
+        out.append(entry)
+    return out, rc
 
 
 def _as_hwc(a, channels, what):
@@ -200,6 +239,54 @@ class ResidentDataset:
         if bad.any():
             raise ValueError(f"selection row {int(np.flatnonzero(bad)[0])}: mirror / vflip must be 0 or 1")
 
+    def check_windows(self, sel, h, w):
+        """Raise unless every row (index, y0, x0, mirror, vflip, hs, ws) of ``sel`` names a pooled image and an hs x ws window inside it
+        that csbsr_gather_resize_u8 may resample to h x w: hs, ws >= 1 and hs <= 8 h, ws <= 8 w (the kernel's tap tables hold 17 taps
+        per axis).  The 7-column sibling of check_selection, for the same reason: the kernel cannot report a bad row."""
+        s = np.asarray(sel)
+        if s.ndim != 2 or s.shape[1] != 7 or s.shape[0] < 1 or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError(f"window table must be integer [B][7], got {s.dtype} {s.shape}")
+        s = s.astype(np.int64)
+        bad = (s[:, 0] < 0) | (s[:, 0] >= len(self.dims))
+        if bad.any():
+            raise ValueError(f"window row {int(np.flatnonzero(bad)[0])}: image index {int(s[bad][0, 0])} outside the pool of {len(self.dims)}")
+        d = self.dims[s[:, 0]].astype(np.int64)
+        bad = (s[:, 5] < 1) | (s[:, 6] < 1)
+        if bad.any():
+            r = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"window row {r}: window size {int(s[r, 5])} x {int(s[r, 6])} must be at least 1 x 1")
+        bad = (s[:, 1] < 0) | (s[:, 1] + s[:, 5] > d[:, 0]) | (s[:, 2] < 0) | (s[:, 2] + s[:, 6] > d[:, 1])
+        if bad.any():
+            r = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"window row {r}: window y0 {int(s[r, 1])} x0 {int(s[r, 2])} of {int(s[r, 5])} x {int(s[r, 6])} leaves image "
+                             f"{int(s[r, 0])} ({int(d[r, 0])} x {int(d[r, 1])})")
+        bad = (s[:, 5] > 8 * h) | (s[:, 6] > 8 * w)
+        if bad.any():
+            r = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"window row {r}: window {int(s[r, 5])} x {int(s[r, 6])} is more than 8 times the output {h} x {w}")
+        bad = ((s[:, 3] != 0) & (s[:, 3] != 1)) | ((s[:, 4] != 0) & (s[:, 4] != 1))
+        if bad.any():
+            raise ValueError(f"window row {int(np.flatnonzero(bad)[0])}: mirror / vflip must be 0 or 1")
+
+    def gather_resized(self, sel_dev, B, h, w, antialias=True):
+        """(hr [B,3,h,w], mask [B,1,h,w]) fp32: the hs x ws window of each row of the int32 [B][7] device table ``sel_dev`` (validated by
+        the caller, check_windows) resampled to h x w like F.interpolate(mode="bilinear", antialias=antialias), / 255.  The mask goes
+        through the same resample (transforms.py:619-620) and comes out soft."""
+        if self.device.type != "cuda":
+            raise L.CsbsrHipError("ResidentDataset.gather_resized needs the pool on a GPU: csbsr_amd has no fallback path")
+        if tuple(sel_dev.shape) != (B, 7) or sel_dev.dtype != torch.int32 or not sel_dev.is_contiguous():
+            raise ValueError(f"window table must be a contiguous int32 [{B}][7] tensor, got {sel_dev.dtype} {tuple(sel_dev.shape)}")
+        L.load()
+        hr = torch.empty(B, 3, h, w, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, 1, h, w, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            L.call("csbsr_gather_resize_u8", _ptr(self.image_pool), _ptr(self.image_offsets_dev), _ptr(self.dims_dev), 3, _ptr(sel_dev),
+                   B, h, w, int(bool(antialias)), _ptr(hr), st)
+            L.call("csbsr_gather_resize_u8", _ptr(self.mask_pool), _ptr(self.mask_offsets_dev), _ptr(self.dims_dev), 1, _ptr(sel_dev),
+                   B, h, w, int(bool(antialias)), _ptr(mask), st)
+        return hr, mask
+
     def gather(self, sel_dev, B, h, w):
         """(hr [B,3,h,w], mask [B,1,h,w]) fp32 = pool bytes / 255 for the int32 [B][5] device table ``sel_dev`` (validated by the caller)."""
         if self.device.type != "cuda":
@@ -216,7 +303,8 @@ class ResidentDataset:
         return hr, mask
 
 
-_ROW = 32          # staged bytes per sample: int32 [5] selection row, then fp32 [3] blur parameters
+_ROW = 32          # staged bytes per sample: int32 [5] selection row, then fp32 [3] blur parameters (40 with the [7] rows of resized_crop)
+_TRIES = 10        # RandomResizedCrop.get_params draws at most ten windows before its central fallback
 _SLOTS = 4         # staging ring: a slot is rewritten four batches after its upload was enqueued
 
 
@@ -244,12 +332,21 @@ class DeviceTrainLoader:
     HAPPENS (the reference's RandomVerticalFlip(p) class flips with probability 1 - p).  Flips act on the whole image and the window is
     taken afterwards (RandomMirror -> ToTensor -> crop).
 
+    ``resized_crop={"scale": (lo, hi), "ratio": (lo, hi)}`` (defaults (0.5, 1.0) / (1.0, 1.0), the reference's class defaults) replaces
+    the fixed window by RandomResizedCrop (transforms.py:607-622): per sample a window of area ``U(scale) * H * W`` and aspect
+    ``exp(U(log ratio))``, drawn as torchvision's published RandomResizedCrop.get_params draws it (ten tries, then the central fallback),
+    and resampled to the crop size by ``csbsr_gather_resize_u8`` -- image AND mask, bilinear with torchvision's antialias default, so the
+    mask comes out soft.  ``draw`` then returns [b,7] rows (..., hs, ws) from a fixed number of uniforms per sample (24), whatever is
+    accepted, and ``batch`` takes such rows.  A non-identity ``RandomResizedCrop`` entry of ``augmentation`` means the same (see
+    split_resized_crop); the explicit argument wins.  Images may be smaller than the crop in this mode (the window is upsampled) but not
+    larger than 8 times the crop per side, the kernel's limit on a window.
+
     The mask is ``bytes / 255`` like the reference's (``mask / 255``, data_preprocess.py:44), so a {0, 255} mask becomes {0, 1}.
     ``blur=False`` (crack_dataset.py:55-58): the kernel target is a delta at the centre, the LR image the down-scaled unblurred crop.
     """
 
     def __init__(self, dataset, crop, scale, ksize=21, *, batch_size, num_iterations=None, blur=True, isotropic=False, augmentation=None,
-                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1), shuffle=True):
+                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1), shuffle=True, resized_crop=None):
         self.dataset = dataset
         self.h, self.w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
         self.scale, self.K = int(scale), int(ksize)
@@ -269,9 +366,19 @@ class DeviceTrainLoader:
         if len(self.indices) == 0:
             raise ValueError(f"shard {shard} of a dataset of {len(dataset)} is empty")
         dims = dataset.dims[self.indices]
-        if (dims[:, 0] < self.h).any() or (dims[:, 1] < self.w).any():
-            raise ValueError(f"an image is smaller than the crop {self.h} x {self.w}")
-        aug = interpret_augmentation(DEFAULT_AUGMENTATION if augmentation is None else augmentation, (self.h, self.w), dims)
+        augmentation, listed = split_resized_crop(DEFAULT_AUGMENTATION if augmentation is None else augmentation)
+        if resized_crop is None:
+            resized_crop = listed
+        self.resized_crop = None if resized_crop is None else _resized_crop_args(resized_crop)
+        if self.resized_crop is None:
+            if (dims[:, 0] < self.h).any() or (dims[:, 1] < self.w).any():
+                raise ValueError(f"an image is smaller than the crop {self.h} x {self.w}")
+        elif (dims[:, 0] > 8 * self.h).any() or (dims[:, 1] > 8 * self.w).any():
+            raise ValueError(f"an image is more than 8 times the crop {self.h} x {self.w} per side: its windows could exceed what "
+                             "csbsr_gather_resize_u8 resamples")
+        # (with resized_crop the entry that stood for it is a RandomCrop by now, or the list has its own crop; the sizes interpret_augmentation
+        # sees only matter for a list without a crop, which resized_crop supplies)
+        aug = interpret_augmentation(augmentation, (self.h, self.w), dims if self.resized_crop is None else np.array([[self.h, self.w]]))
         self.mirror_p = aug["mirror_p"]
         self.gen = torch.Generator(device="cpu")
         if seed is not None:
@@ -280,6 +387,7 @@ class DeviceTrainLoader:
         self.deg = DeviceDegradation(self.scale, ksize=self.K, isotropic=isotropic, antialias=antialias, device=self.device)
         self.deg.gen = self.gen          # one generator for every draw
         self.antialias = bool(antialias)
+        self.resize_antialias = True          # of the window's resample: torchvision's default for tensors since 0.17
         self._perm, self._cursor, self._produced, self._resumed = None, 0, 0, False
         self._ring, self._slot = [None] * _SLOTS, 0
 
@@ -307,10 +415,12 @@ class DeviceTrainLoader:
 
     def draw(self, B=None):
         """Decisions of the next batch: (sel int32 [b,5] = (pool index, y0, x0, mirror, vflip), blur_params fp32 [b,3]) with b <= B
-        (b < B only at the end of an epoch)."""
+        (b < B only at the end of an epoch).  With ``resized_crop`` the rows are [b,7]: (..., hs, ws), the window's size."""
         idx = self._next_indices(self.batch_size if B is None else int(B))
         b = len(idx)
         dims = self.dataset.dims[idx].astype(np.int64)
+        if self.resized_crop is not None:
+            return self._draw_windows(idx, dims), self.deg.draw_params(b)
         u = torch.rand(b, 4, generator=self.gen, dtype=torch.float64).numpy()
         span_y, span_x = dims[:, 0] - self.h, dims[:, 1] - self.w
         sel = np.empty((b, 5), dtype=np.int32)
@@ -321,33 +431,67 @@ class DeviceTrainLoader:
         sel[:, 4] = u[:, 3] < self.vflip_p
         return torch.from_numpy(sel), self.deg.draw_params(b)
 
+    def _draw_windows(self, idx, dims):
+        """[b,7] rows for the pool indices ``idx``: RandomResizedCrop.get_params per sample out of 24 uniforms -- (area, aspect) of
+        _TRIES tries, the offset pair, the two flips -- all drawn whatever is accepted, so the generator advances by the same amount for
+        every batch of b samples.  The first try whose rounded window fits the image is taken, else the central fallback."""
+        b = len(idx)
+        (s_lo, s_hi), (r_lo, r_hi) = self.resized_crop
+        u = torch.rand(b, 2 * _TRIES + 4, generator=self.gen, dtype=torch.float64).numpy()
+        H, W = dims[:, 0], dims[:, 1]
+        t = (H * W)[:, None] * (s_lo + (s_hi - s_lo) * u[:, 0:2 * _TRIES:2])
+        r = np.exp(np.log(r_lo) + (np.log(r_hi) - np.log(r_lo)) * u[:, 1:2 * _TRIES:2])
+        ws, hs = np.rint(np.sqrt(t * r)).astype(np.int64), np.rint(np.sqrt(t / r)).astype(np.int64)
+        ok = (ws > 0) & (ws <= W[:, None]) & (hs > 0) & (hs <= H[:, None])
+        first = np.argmax(ok, axis=1)
+        took = ok[np.arange(b), first]
+        hs, ws = hs[np.arange(b), first], ws[np.arange(b), first]
+        # the fallback: the largest central window whose aspect is inside the ratio range
+        in_ratio = W / H
+        fb_w = np.where(in_ratio > r_hi, np.rint(H * r_hi).astype(np.int64), W)
+        fb_h = np.where(in_ratio < r_lo, np.rint(W / r_lo).astype(np.int64), H)
+        hs, ws = np.where(took, hs, fb_h), np.where(took, ws, fb_w)
+        span_y, span_x = H - hs, W - ws
+        sel = np.empty((b, 7), dtype=np.int32)
+        sel[:, 0] = idx
+        sel[:, 1] = np.where(took, np.minimum((u[:, -4] * (span_y + 1)).astype(np.int64), span_y), span_y // 2)
+        sel[:, 2] = np.where(took, np.minimum((u[:, -3] * (span_x + 1)).astype(np.int64), span_x), span_x // 2)
+        sel[:, 3] = u[:, -2] < self.mirror_p
+        sel[:, 4] = u[:, -1] < self.vflip_p
+        sel[:, 5], sel[:, 6] = hs, ws
+        return torch.from_numpy(sel)
+
     # ------------------------------------------------------------------------------------------------------------- tensors (device)
     def _upload(self, sel, params):
-        """sel int32 [B,5] + params fp32 [B,3] -> device views, through a pinned staging slot and ONE non-blocking copy.  Before a
+        """sel int32 [B,5] (or [B,7]) + params fp32 [B,3] -> device views, through a pinned staging slot and ONE non-blocking copy.  Before a
         slot is rewritten the host waits for the upload issued from it _SLOTS batches earlier (the pinned bytes must not change under a
         copy in flight, as in csbsr_amd/optim.py): the only host wait on the device here, and one that blocks only a host running more
         than _SLOTS batches ahead of the device."""
-        B = sel.shape[0]
+        B, cols = sel.shape
+        row = 4 * cols + 12          # = _ROW for the [5] rows
         slot = self._ring[self._slot]
-        if slot is None or slot[0].numel() < B * _ROW:
-            n = max(B, self.batch_size) * _ROW
+        if slot is None or slot[0].numel() < B * row:
+            n = max(B, self.batch_size) * row
             slot = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=self.device), torch.cuda.Event()]
             self._ring[self._slot] = slot
         else:
             slot[2].synchronize()          # (this slot's upload was enqueued _SLOTS batches ago: normally long consumed)
         self._slot = (self._slot + 1) % _SLOTS
         host, dev, ev = slot
-        host[:B * 20].view(torch.int32).view(B, 5).copy_(sel)
-        host[B * 20:B * _ROW].view(torch.float32).view(B, 3).copy_(params)
-        dev[:B * _ROW].copy_(host[:B * _ROW], non_blocking=True)
+        host[:B * 4 * cols].view(torch.int32).view(B, cols).copy_(sel)
+        host[B * 4 * cols:B * row].view(torch.float32).view(B, 3).copy_(params)
+        dev[:B * row].copy_(host[:B * row], non_blocking=True)
         ev.record(torch.cuda.current_stream(self.device))
-        return dev[:B * 20].view(torch.int32).view(B, 5), dev[B * 20:B * _ROW].view(torch.float32).view(B, 3)
+        return dev[:B * 4 * cols].view(torch.int32).view(B, cols), dev[B * 4 * cols:B * row].view(torch.float32).view(B, 3)
 
     def batch(self, sel, blur_params=None):
-        """Decisions -> (x_lr [B,3,h/s,w/s], hr [B,3,h,w], mask [B,1,h,w], kernels [B,1,K,K], sdf [B,1,h,w]).  ``sel`` is validated on the
-        host first.  No wait on the batch's own work: the host may only block on the upload issued four batches earlier (_upload)."""
+        """Decisions -> (x_lr [B,3,h/s,w/s], hr [B,3,h,w], mask [B,1,h,w], kernels [B,1,K,K], sdf [B,1,h,w]).  ``sel`` ([B,5], or [B,7] with
+        ``resized_crop``) is validated on the host first.  No wait on the batch's own work: the host may only block on the upload issued four batches earlier (_upload)."""
         sel = torch.as_tensor(sel)
-        self.dataset.check_selection(sel.numpy(), self.h, self.w)
+        if self.resized_crop is not None:
+            self.dataset.check_windows(sel.numpy(), self.h, self.w)
+        else:
+            self.dataset.check_selection(sel.numpy(), self.h, self.w)
         if self.device.type != "cuda":
             raise L.CsbsrHipError("DeviceTrainLoader.batch needs the dataset on a GPU: csbsr_amd has no fallback path")
         sel = sel.to(torch.int32)
@@ -360,7 +504,10 @@ class DeviceTrainLoader:
             params = torch.zeros(B, 3)
         with torch.cuda.device(self.device):
             sel_dev, params_dev = self._upload(sel, params)
-            hr, mask = self.dataset.gather(sel_dev, B, self.h, self.w)
+            if self.resized_crop is not None:
+                hr, mask = self.dataset.gather_resized(sel_dev, B, self.h, self.w, self.resize_antialias)
+            else:
+                hr, mask = self.dataset.gather(sel_dev, B, self.h, self.w)
             if self.blur:
                 return self.deg(hr, mask, params=params_dev)
             k = torch.zeros(B, 1, self.K, self.K, dtype=torch.float32, device=self.device)

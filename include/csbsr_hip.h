@@ -517,6 +517,20 @@ int csbsr_gaussian_kernels(const float* params, float* out, int32_t N, int32_t K
  * out fp32 [B][channels][h][w]. */
 int csbsr_gather_crop_u8(const uint8_t* pool, const int64_t* offsets, const int32_t* dims, int32_t channels, const int32_t* sel,
                          int32_t B, int32_t h, int32_t w, float* out, csbsr_stream_t s);
+/* The same selection with a resample: sel int32 [B][7] = (index, y0, x0, mirror, vflip, hs, ws) names the hs x ws window at (y0, x0) of
+ * the flipped image (coordinates as for csbsr_gather_crop_u8), and out[b][c] is that window resampled to h x w and divided by 255:
+ *   F.interpolate(window, (h, w), mode="bilinear", align_corners=False, antialias=bool(antialias)) / 255
+ * as torch evaluates it on the CPU in fp32 -- RandomResizedCrop (transforms.py:607-622) and `image / 255`.  Separable, horizontal pass
+ * first; along an axis of n_in source and n_out output samples, s = n_in / n_out, support = inv^-1 = s where antialias and s >= 1, else 1:
+ *   c = s (o + 0.5),  taps j in [max(0, int(c - support + 0.5)), min(n_in, int(c + support + 0.5))),
+ *   w_j = max(0, 1 - |(j - c + 0.5) inv|) / sum_j (the same),  added in ascending j.
+ * A window of the output size has weights {1, 0}: the result then equals csbsr_gather_crop_u8's bit for bit.  One launch, no intermediate
+ * in device memory, no atomics: run-to-run bit-reproducible.  Limits: hs <= 8 h and ws <= 8 w (at most 17 taps per axis); the rows live
+ * in device memory, so the CALLER enforces this (ResidentDataset.check_windows) -- a row over the limit gives wrong pixels, never a wrong
+ * address.  Source coordinates are clamped into the image as above (a window that overhangs its image replicates the border); the image
+ * index is the caller's responsibility alone.  out fp32 [B][channels][h][w]. */
+int csbsr_gather_resize_u8(const uint8_t* pool, const int64_t* offsets, const int32_t* dims, int32_t channels, const int32_t* sel,
+                           int32_t B, int32_t h, int32_t w, int32_t antialias, float* out, csbsr_stream_t s);
 /* Evaluation outputs (csrc/eval_io.hip).  Stitch the model's patch batch back into images: JointPatch (patch_sampler.py:30-51), the two
  * masked clip assignments of inference.py:94-95 and ToPILImage's mul(255).byte() with its CHW -> HWC in one pass.
  *   patches fp32 [B][nH][nW][C][ph][pw]: patch (iy, ix) of image b is batch entry b * nH * nW + iy * nW + ix; C is 1 or 3
