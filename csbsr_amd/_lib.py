@@ -168,6 +168,7 @@ SIGNATURES = {
     "csbsr_head1_bwd_input": (i32, [vp, i64, vp, i32, vp, i64, i64, vp]),
     "csbsr_adam_step": (i32, [vp, vp, vp, i32, C.c_double, C.c_double, C.c_float, vp]),
     "csbsr_sgd_step": (i32, [vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, vp]),
+    "csbsr_fingerprint": (i32, [vp, vp, vp, i32, vp, vp]),
 }
 
 # private hooks (csbsr_amd/csrc/csbsr_debug.h): kernel selection for A/B timing and kernel attribution for bench.py

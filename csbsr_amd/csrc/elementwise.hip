@@ -363,6 +363,61 @@ extern "C" int csbsr_sgd_step(const csbsr_sgd_tensor_t* tensors, const int32_t* 
   CSBSR_LAUNCH_CHECK("csbsr_sgd_step");
   return 0;
 }
+// ---- multi-tensor fingerprint (csbsr_hip.h): the chunk map of the two optimiser kernels above, read-only.  Per workgroup the two sums of
+// its <= 8192 words (64-bit integers, wrapping), folded wave shuffle -> LDS -> ONE pair of 64-bit integer atomic adds per workgroup onto
+// the tensor's zeroed row.  Addition modulo 2^64 is associative and commutative, so neither the chunk size, nor the block size, nor the
+// order in which workgroups retire can change a bit of the result (unlike a floating-point atomic sum).  No floating point anywhere.
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+__global__ __launch_bounds__(256) void fingerprint_kernel(const csbsr_fp_tensor_t* __restrict__ tt, const int* __restrict__ bt,
+                                                          const int* __restrict__ bc, unsigned long long* __restrict__ out) {
+  typedef unsigned long long u64;
+  const int ti = bt[blockIdx.x];
+  const csbsr_fp_tensor_t t = tt[ti];
+  const long base = (long)bc[blockIdx.x] * ADAM_CHUNK;
+  const long rem = t.n - base;
+  const int cnt = rem < ADAM_CHUNK ? (rem > 0 ? (int)rem : 0) : ADAM_CHUNK;
+  u64 s0 = 0, s1 = 0;
+  const int nv = t.vec ? cnt >> 2 : 0;
+  const uint4* w4 = reinterpret_cast<const uint4*>(t.w + base);
+  for (int i = threadIdx.x; i < nv; i += 256) {
+    const uint4 w = w4[i];
+    const u64 j1 = (u64)(base + 4 * i) + 1;          // (index of w.x) + 1
+    s0 += (u64)w.x + (u64)w.y + (u64)w.z + (u64)w.w;
+    s1 += (u64)w.x * j1 + (u64)w.y * (j1 + 1) + (u64)w.z * (j1 + 2) + (u64)w.w * (j1 + 3);
+  }
+  for (int i = 4 * nv + threadIdx.x; i < cnt; i += 256) {
+    const u64 w = t.w[base + i];
+    s0 += w;
+    s1 += w * ((u64)(base + i) + 1);
+  }
+  s0 = wave_sum_u64(s0);
+  s1 = wave_sum_u64(s1);
+  __shared__ u64 part[4][2];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { part[wave][0] = s0; part[wave][1] = s1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(out + 2 * (long)ti, part[0][0] + part[1][0] + part[2][0] + part[3][0]);
+    atomicAdd(out + 2 * (long)ti + 1, part[0][1] + part[1][1] + part[2][1] + part[3][1]);
+  }
+}
+extern "C" int csbsr_fingerprint(const csbsr_fp_tensor_t* tensors, const int32_t* block_tensor, const int32_t* block_chunk, int32_t nblocks,
+                                 uint64_t* out, csbsr_stream_t s) {
+  CSBSR_CHECK(tensors && block_tensor && block_chunk && out && nblocks >= 0, "fingerprint: bad arguments");
+  if (nblocks == 0) return 0;
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit atomics");
+  hipLaunchKernelGGL(fingerprint_kernel, dim3(nblocks), dim3(256), 0, reinterpret_cast<hipStream_t>(s), tensors, block_tensor, block_chunk,
+                     reinterpret_cast<unsigned long long*>(out));
+  CSBSR_LAUNCH_CHECK("csbsr_fingerprint");
+  return 0;
+}
 
 extern "C" int csbsr_axpby_split(int64_t npix, int32_t c, const void* x, int64_t x_ld, int64_t x_lo, float a, const void* z, int64_t z_ld,
                                  int64_t z_lo, float b, void* y, int64_t y_ld, int64_t y_lo, csbsr_stream_t s) {

@@ -320,6 +320,18 @@ class DeviceTrainLoader:
     another loader (a resumed run).  ``shard=(rank, world)`` keeps the samples at positions
     ``i % world == rank`` of ``dataset``, so data-parallel ranks see disjoint data.
 
+    ``shard_mode="batch"`` shards the BATCH instead of the dataset: every rank runs the decision sequence of ONE loader with batch
+    ``world * batch_size`` over the whole dataset -- the same seeded generator, the same permutation, the same window, flip and blur
+    draws -- and keeps rows ``[rank * batch_size, (rank + 1) * batch_size)`` of each global batch.  The rows of step t, concatenated over
+    the ranks, are therefore exactly what the single loader with ``batch_size = world * b`` and the same seed yields: a data-parallel run
+    IS the single-GPU experiment with the same global batch (under ``"sample"``, the default, each rank permutes its own subset and the
+    samples of step t depend on the world size).  The generator advances identically on every rank and ``state_dict()`` is the same on
+    every rank; it carries ``"global_batch"``, and loads into a loader of any ``world`` whose ``world * batch_size`` is that number (a
+    run continued on another number of GPUs) and into no other.  ``len()`` and ``produced`` count global batches.  Ranks must present
+    equal shards to the gradient exchange, so ``shuffle=True`` with ``world > 1`` needs ``drop_last=True`` (ValueError otherwise).
+    ``shuffle=False`` (validation) may end with a short global batch; it is split by the same contiguous rule, a rank's slice may be
+    shorter or empty, and for a global batch of which the rank holds nothing the loader yields ``None`` in place of a batch.
+
     Every draw comes from ONE seeded host ``torch.Generator`` (the blur parameters too: DeviceDegradation.draw_params is handed the same
     generator).  A crop offset is uniform on [0, H-h] x [0, W-w], as torchvision's RandomCrop.get_params draws it; the mirror has p = 0.5.
     ``draw(B)`` makes the decisions of the next batch -- a [B,5] int32 table (pool index, y0, x0, mirror, vflip) and the [B,3] blur
@@ -346,7 +358,8 @@ class DeviceTrainLoader:
     """
 
     def __init__(self, dataset, crop, scale, ksize=21, *, batch_size, num_iterations=None, blur=True, isotropic=False, augmentation=None,
-                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1), shuffle=True, resized_crop=None):
+                 vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1), shuffle=True, resized_crop=None,
+                 shard_mode="sample"):
         self.dataset = dataset
         self.h, self.w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
         self.scale, self.K = int(scale), int(ksize)
@@ -362,7 +375,18 @@ class DeviceTrainLoader:
         rank, world = (int(v) for v in shard)
         if not 0 <= rank < world:
             raise ValueError(f"shard {shard}: need 0 <= rank < world")
-        self.indices = np.asarray(dataset.indices[rank::world], dtype=np.int64)             # pool indices of this shard
+        if shard_mode not in ("sample", "batch"):
+            raise ValueError(f"shard_mode {shard_mode!r}: 'sample' or 'batch'")
+        self.shard_mode, self.rank, self.world = shard_mode, rank, world
+        if shard_mode == "batch":
+            if self.shuffle and world > 1 and not self.drop_last:
+                raise ValueError("shard_mode='batch' with shuffle=True and world > 1 needs drop_last=True: a short global batch at the end "
+                                 "of an epoch would leave the ranks unequal shards")
+            self.indices = np.asarray(dataset.indices, dtype=np.int64)                      # the whole dataset: the rank keeps rows, not samples
+            self._step_batch = world * self.batch_size                                      # rows one step of the decision sequence draws
+        else:
+            self.indices = np.asarray(dataset.indices[rank::world], dtype=np.int64)         # pool indices of this shard
+            self._step_batch = self.batch_size
         if len(self.indices) == 0:
             raise ValueError(f"shard {shard} of a dataset of {len(dataset)} is empty")
         dims = dataset.dims[self.indices]
@@ -415,8 +439,9 @@ class DeviceTrainLoader:
 
     def draw(self, B=None):
         """Decisions of the next batch: (sel int32 [b,5] = (pool index, y0, x0, mirror, vflip), blur_params fp32 [b,3]) with b <= B
-        (b < B only at the end of an epoch).  With ``resized_crop`` the rows are [b,7]: (..., hs, ws), the window's size."""
-        idx = self._next_indices(self.batch_size if B is None else int(B))
+        (b < B only at the end of an epoch).  With ``resized_crop`` the rows are [b,7]: (..., hs, ws), the window's size.  B defaults to
+        what one step draws: ``batch_size``, or under ``shard_mode="batch"`` the GLOBAL batch (``shard_rows`` takes the rank's rows)."""
+        idx = self._next_indices(self._step_batch if B is None else int(B))
         b = len(idx)
         dims = self.dataset.dims[idx].astype(np.int64)
         if self.resized_crop is not None:
@@ -520,27 +545,39 @@ class DeviceTrainLoader:
         if self.num_iterations is not None:
             return self.num_iterations
         n = len(self.indices)
-        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+        return n // self._step_batch if self.drop_last else -(-n // self._step_batch)
 
     @property
     def produced(self):
-        """batches produced so far by the running (or loaded) sequence"""
+        """batches (global batches under ``shard_mode="batch"``) produced so far by the running (or loaded) sequence"""
         return self._produced
 
+    def shard_rows(self, sel, params):
+        """This rank's rows of a global batch's decisions, or None when it holds none of them (a short last validation batch)."""
+        lo = self.rank * self.batch_size
+        sel, params = sel[lo:lo + self.batch_size], params[lo:lo + self.batch_size]
+        return None if sel.shape[0] == 0 else (sel, params)
+
     def iter_decisions(self):
-        """The (sel, blur_params) sequence __iter__ turns into batches (host only)."""
+        """The (sel, blur_params) sequence __iter__ turns into batches (host only).  Under ``shard_mode="batch"`` every rank steps
+        through the same global sequence and an item is the rank's rows of it, or None."""
+        if self.shard_mode == "batch":
+            return (self.shard_rows(sel, params) for sel, params in self._iter_steps())
+        return self._iter_steps()
+
+    def _iter_steps(self):
         if self._resumed:          # a loaded state continues: same permutation, cursor and count (the generator was restored with them)
             self._resumed = False
             if self.num_iterations is None and self._perm is not None and self._cursor >= len(self._perm):
                 return             # (saved after the last batch of the single pass)
         else:
             self._perm, self._produced = None, 0
-        if self.drop_last and len(self.indices) < self.batch_size:
+        if self.drop_last and len(self.indices) < self._step_batch:
             return
         while self.num_iterations is None or self._produced < self.num_iterations:
-            sel, params = self.draw(self.batch_size)
+            sel, params = self.draw(self._step_batch)
             last = self._cursor >= len(self._perm)
-            if not (self.drop_last and sel.shape[0] < self.batch_size):
+            if not (self.drop_last and sel.shape[0] < self._step_batch):
                 self._produced += 1
                 yield sel, params
             if last and self.num_iterations is None:
@@ -548,13 +585,23 @@ class DeviceTrainLoader:
 
     def state_dict(self):
         """What the decision sequence depends on, taken between two batches: the generator, the running epoch's permutation (pool
-        indices), the cursor in it and the number of batches produced.  Tensors and ints only."""
-        return {"generator": self.gen.get_state().clone(), "perm": None if self._perm is None else torch.from_numpy(np.array(self._perm)),
-                "cursor": int(self._cursor), "produced": int(self._produced), "samples": len(self.indices)}
+        indices), the cursor in it and the number of batches produced.  Tensors and ints only.  Under ``shard_mode="batch"`` also
+        ``"global_batch"`` = world * batch_size, and the whole dict is the same on every rank."""
+        state = {"generator": self.gen.get_state().clone(), "perm": None if self._perm is None else torch.from_numpy(np.array(self._perm)),
+                 "cursor": int(self._cursor), "produced": int(self._produced), "samples": len(self.indices)}
+        if self.shard_mode == "batch":
+            state["global_batch"] = int(self._step_batch)
+        return state
 
     def load_state_dict(self, state):
         """Continue another loader's sequence: the next ``iter_decisions`` / ``__iter__`` of this loader goes on where that one stopped
-        instead of starting over.  The loader must have been built over the same shard with the same arguments."""
+        instead of starting over.  The loader must have been built over the same shard with the same arguments -- under
+        ``shard_mode="batch"``: over the same dataset with the same GLOBAL batch, whatever the world size."""
+        if (self.shard_mode == "batch") != ("global_batch" in state):
+            raise ValueError(f"loader state of shard_mode {'batch' if 'global_batch' in state else 'sample'!r}, this loader's is {self.shard_mode!r}")
+        if self.shard_mode == "batch" and int(state["global_batch"]) != self._step_batch:
+            raise ValueError(f"loader state of global batch {int(state['global_batch'])}, this loader's is {self.world} x {self.batch_size} = "
+                             f"{self._step_batch}")
         perm = state["perm"]
         if int(state["samples"]) != len(self.indices) or (perm is not None and len(perm) != len(self.indices)):
             raise ValueError(f"loader state of a shard of {int(state['samples'])} samples, this shard has {len(self.indices)}")
@@ -565,6 +612,6 @@ class DeviceTrainLoader:
         self._cursor, self._produced, self._resumed = int(state["cursor"]), int(state["produced"]), True
 
     def __iter__(self):
-        for sel, params in self.iter_decisions():
-            yield self.batch(sel, params)
+        for item in self.iter_decisions():
+            yield None if item is None else self.batch(*item)
 

@@ -17,16 +17,26 @@ What differs, on purpose: the running loss sums stay on the device (fp64, the re
 ``log_step`` -- the reference's two ``.item()`` per step make the host wait for every step; no W&B; a third checkpoint file carries what an exact
 continuation needs (``resume``); ``resume`` also loads the optimiser file, which the reference writes and never reads.
 
-Out of scope: data-parallel wiring (``GradBucketReducer`` still works in a caller's own loop), the first-batch PNG dumps of trainer.py:186-227,
-``do_pretrain_sr`` / ``SRModelWithLoss``, and every cfg value the model constructors refuse (they keep raising there).
+Data-parallel (one process per GPU, ``torch.distributed`` initialised with world > 1, or CSBSR_FORCE_DIST=1): ``do_train`` attaches the
+``GradBucketReducer``, broadcasts rank 0's weights and checks with ``csbsr_amd.parallel.agree`` (a device fingerprint per tensor and a few KB
+of all-reduce) that the replicas hold the same bits -- at the start and again before every checkpoint, which rank 0 alone writes.  Logged
+losses and validation results are those of the GLOBAL batch.  With ``DeviceTrainLoader(shard_mode="batch")`` the run is the single-GPU run
+with the same global batch, and its checkpoints continue on another number of GPUs (``resume``).
+
+Out of scope: the first-batch PNG dumps of trainer.py:186-227, ``do_pretrain_sr`` / ``SRModelWithLoss``, and every cfg value the model
+constructors refuse (they keep raising there).
 """
 import datetime
 import os
 import time
+import warnings
 
 import torch
+import torch.distributed as dist
 from torch.optim.lr_scheduler import LambdaLR
 
+from .parallel import agree
+from .parallel.reducer import GradBucketReducer, broadcast_parameters, _forced
 from .utils.lr_scheduler import UpDownScheduler
 from .utils.misc import fix_model_state_dict
 
@@ -118,25 +128,102 @@ def _device_of(model):
     return torch.device(dev)
 
 
+# ------------------------------------------------------------------------------------------------------------------ data-parallel
+def _dist(process_group=None):
+    """(group, rank, world) when the data-parallel path is on -- torch.distributed initialised with more than one rank, or
+    CSBSR_FORCE_DIST=1, the switch GradBucketReducer honours, which puts the real backend under the calls of a one-rank group -- else
+    (None, 0, 1)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return None, 0, 1
+    world = dist.get_world_size(process_group)
+    if world == 1 and not _forced():
+        return None, 0, 1
+    return (dist.group.WORLD if process_group is None else process_group), dist.get_rank(process_group), world
+
+
+def replica_tensors(model, optimizer=None, running_stats=True):
+    """[(name, tensor)] of everything that must be the same on every replica: parameters and buffers (``state_dict()`` names) and, with an
+    optimiser, its state tensors on the model's device (``optimizer.<group>.<index>.<key>``; host-side scalars such as Adam's ``step``
+    follow from the common skip decision and are left out).  ``running_stats=False`` leaves out BatchNorm's ``running_mean`` /
+    ``running_var``: once training has begun they are per replica BY DESIGN -- each replica normalises with, and averages, the statistics
+    of its own shard, as the replicas of the reference's nn.DataParallel do, and rank 0's are the ones that are saved, as there."""
+    dev = _device_of(model)
+    out = [(k, v.detach()) for k, v in model.state_dict().items()
+           if torch.is_tensor(v) and (running_stats or not k.endswith((".running_mean", ".running_var")))]
+    if optimizer is not None:
+        for gi, group in enumerate(optimizer.param_groups):
+            for pi, p in enumerate(group["params"]):
+                for key, v in optimizer.state.get(p, {}).items():
+                    if torch.is_tensor(v) and v.device.type == dev.type and v.dim() > 0:
+                        out.append((f"optimizer.{gi}.{pi}.{key}", v.detach()))
+    return out
+
+
+def _device_rng(dev):
+    return torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None
+
+
 # ------------------------------------------------------------------------------------------------------------------ validation
 class ValidationAccumulator:
     """The bookkeeping of one validation pass (trainer.py:142-149, 160-183, 230-234).  ``add`` takes one batch: its two per-sample loss
     vectors and its four per-sample metric vectors, on any device, and keeps them there; ``result`` reads everything back at once.
 
     The losses are means over BATCHES of the batch means (a short last batch weighs as much as a full one); the metrics are means over
-    IMAGES.  The host arithmetic is the reference's: fp64 running sums in order of arrival."""
+    IMAGES.  The host arithmetic is the reference's: fp64 running sums in order of arrival.
+
+    With a ``process_group`` every rank adds ITS rows of each global batch (``add_empty`` where it holds none: the short last batch of a
+    ``shard_mode="batch"`` loader) and keeps, in fp64 on the device, ``[sum seg, sum sr, count]`` per global batch plus the four metric
+    sums and the image count; ``result`` makes ONE SUM all-reduce of that table and aggregates as above over the GLOBAL batches:
+    per-batch loss = sum / count, then the mean over batches; metrics are sums / images.  Every rank gets the same numbers, those of a
+    one-rank pass over the same global batches (up to the rounding of the per-batch means, fp64 here where a one-rank pass takes an fp32
+    mean).  Every rank must add the same number of batches.  ``device``: where the table lives when the rank saw nothing but empty slices."""
 
     METRICS = ("psnr", "ssim", "kernel_psnr", "iou")
 
-    def __init__(self):
+    def __init__(self, process_group=None, device=None):
         self.losses, self.metrics = [], {k: [] for k in self.METRICS}
+        self.pg, self.device = process_group, device
+        self.rows, self.totals = [], None          # with a process group: fp64 [3] per global batch (None: a zero row), fp64 [5] metric sums + images
+
+    def add_empty(self):
+        """a global batch of which this rank holds nothing"""
+        if self.pg is None:
+            raise ValueError("an empty slice exists only in a data-parallel validation pass")
+        self.rows.append(None)
 
     def add(self, segment_loss, sr_loss, psnr, ssim, kernel_psnr, iou):
+        if self.pg is not None:
+            seg, sr = torch.as_tensor(segment_loss).double().reshape(-1), torch.as_tensor(sr_loss).double().reshape(-1)
+            self.rows.append(torch.stack([seg.sum(), sr.sum(), seg.new_tensor(float(seg.numel()))]))
+            ms = [torch.as_tensor(v).float().reshape(-1).double() for v in (psnr, ssim, kernel_psnr, iou)]
+            tot = torch.stack([m.sum() for m in ms] + [seg.new_tensor(float(ms[0].numel()))])
+            self.totals = tot if self.totals is None else self.totals + tot
+            return
         self.losses.append(torch.stack([torch.as_tensor(segment_loss).float().mean(), torch.as_tensor(sr_loss).float().mean()]))
         for k, v in zip(self.METRICS, (psnr, ssim, kernel_psnr, iou)):
             self.metrics[k].append(torch.as_tensor(v).float().reshape(-1))
 
+    def _result_reduced(self):
+        if not self.rows:
+            raise ValueError("validation saw no batch")
+        dev = next((r.device for r in self.rows if r is not None), torch.device("cpu") if self.device is None else torch.device(self.device))
+        zero = torch.zeros(3, dtype=torch.float64, device=dev)
+        table = torch.cat([zero if r is None else r for r in self.rows] + [torch.zeros(5, dtype=torch.float64, device=dev) if self.totals is None
+                                                                          else self.totals])
+        dist.all_reduce(table, op=dist.ReduceOp.SUM, group=self.pg)
+        flat = table.cpu().tolist()
+        nb = len(self.rows)
+        rows, totals = [flat[3 * i:3 * i + 3] for i in range(nb)], flat[3 * nb:]
+        n = int(round(totals[4]))
+        out = {"eval_segment_loss": sum(r[0] / r[2] for r in rows) / nb, "eval_sr_loss": sum(r[1] / r[2] for r in rows) / nb}
+        for i, k in enumerate(self.METRICS):
+            out[k] = totals[i] / n
+        out["batches"], out["images"] = nb, n
+        return out
+
     def result(self):
+        if self.pg is not None:
+            return self._result_reduced()
         if not self.losses:
             raise ValueError("validation saw no batch")
         nb = len(self.losses)
@@ -150,23 +237,31 @@ class ValidationAccumulator:
         return out
 
 
-def validate(model, loader, iteration, *, seed=None):
+def validate(model, loader, iteration, *, seed=None, process_group=None):
     """One pass over ``loader`` (batches of ``(x, hr, mask, k[, sdf])``) with the model in ``eval()`` under ``no_grad``: validation
     segmentation and SR loss, PSNR, SSIM, kernel PSNR and IoU at 0.5 (trainer.py:140-235).  The SR image and the kernel are clamped to
     [0, 1] before their metrics; the segmentation map is binarised with ``>= 0.5`` first (``iou_sweep`` alone compares with ``>``).
 
     ``seed``: when not None the loader's generator is re-seeded with it first, so successive validations see the same crops and blurs and
     are comparable; None is the reference's behaviour, fresh draws in every pass.  The model's mode is restored; ``iter_cnt`` is not touched
-    (``do_train`` switches it off around the call, as the reference does)."""
+    (``do_train`` switches it off around the call, as the reference does).
+
+    Data-parallel (see ``_dist``; ``process_group`` None is the default group): ``loader`` is this rank's
+    ``DeviceTrainLoader(shuffle=False, shard=(rank, world), shard_mode="batch")``, every rank walks the same global batches (a None
+    batch is one of which the rank holds nothing: no forward) and gets the result over all of them (ValidationAccumulator)."""
     from .utils.estimate_metrics import iou_sweep, psnr_ssim
     if seed is not None:
         loader.gen.manual_seed(int(seed))
     was_training = model.training
-    acc = ValidationAccumulator()
+    pg = _dist(process_group)[0]
+    acc = ValidationAccumulator() if pg is None else ValidationAccumulator(pg, _device_of(model))
     model.eval()
     try:
         with torch.no_grad():
             for batch in loader:
+                if batch is None:
+                    acc.add_empty()
+                    continue
                 x, hr, mask, k = batch[:4]
                 extra = {"segment_sdf": batch[4]} if len(batch) > 4 else {}
                 seg_l, sr_l, seg, sr, kp = model(iteration, x, sr_targets=hr, segment_targets=mask, kernel_targets=k, **extra)
@@ -191,16 +286,26 @@ def _trainer_state(model, train_loader, iteration, sums, overflowed):
         "iteration": int(iteration),
         "ss_loss_fn": None if fn is None else {"alpha": fn.alpha, "iter": fn.iter, "fix_alpha": fn.fix_alpha},
         "loader": train_loader.state_dict() if hasattr(train_loader, "state_dict") else None,
-        "cuda_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,          # Dropout2d's masks are drawn from it
+        "cuda_rng": _device_rng(dev),          # Dropout2d's masks are drawn from it
         "cpu_rng": torch.get_rng_state(),
         "loss_scale": {k: getattr(model, k) for k in ("grad_scale", "scale_backoff", "overflow_steps") if hasattr(model, k)},
         "logging": {"sums": sums.detach().cpu(), "overflowed": int(overflowed)},
     }
 
 
-def save_checkpoint(output_dir, iteration, model, optimizer, train_loader=None, sums=None, overflowed=0):
+def save_checkpoint(output_dir, iteration, model, optimizer, train_loader=None, sums=None, overflowed=0, process_group=None):
     """``model/``, ``optimizer/`` (the reference's two files: plain state_dicts, loadable there and by torch.optim.Adam / SGD) and
-    ``trainer/iteration_N.pth`` (everything else ``resume`` needs to continue exactly).  Returns the three paths."""
+    ``trainer/iteration_N.pth`` (everything else ``resume`` needs to continue exactly).  Returns the three paths.
+
+    Data-parallel (see ``_dist``) this is a collective every rank calls: first ``assert_replicas_agree`` over parameters, buffers and the
+    optimiser's state tensors (all but BatchNorm's running statistics, see ``replica_tensors``) -- ReplicaMismatch on every rank, and no
+    file of this iteration, when a replica has drifted --, then rank 0
+    writes the three files and a barrier follows.  The trainer file gains ``"world"`` and ``"ranks"``: per rank the device's and the
+    host's generator state and, for a loader that is not in ``shard_mode="batch"`` (whose state is common), the rank's loader state.
+    ``"logging"`` then holds the window sums of the GLOBAL batch (one more SUM all-reduce of two numbers)."""
+    pg, rank, world = _dist(process_group)
+    if pg is not None:
+        return _save_checkpoint_dp(output_dir, iteration, model, optimizer, train_loader, sums, overflowed, pg, rank, world)
     paths = _paths(output_dir, iteration)
     for p in paths.values():
         os.makedirs(os.path.dirname(p), exist_ok=True)
@@ -211,7 +316,30 @@ def save_checkpoint(output_dir, iteration, model, optimizer, train_loader=None, 
     return paths
 
 
-def resume(cfg, output_dir, iteration, model, optimizer, train_loader):
+def _save_checkpoint_dp(output_dir, iteration, model, optimizer, train_loader, sums, overflowed, pg, rank, world):
+    agree.assert_replicas_agree(replica_tensors(model, optimizer, running_stats=False), pg, what=f"replicas at the checkpoint of iteration {iteration}")
+    dev = _device_of(model)
+    sums = torch.zeros(2, dtype=torch.float64, device=dev) if sums is None else sums.detach().clone()
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=pg)
+    sums = sums / world
+    per_rank = getattr(train_loader, "shard_mode", None) != "batch" and hasattr(train_loader, "state_dict")
+    mine = {"cuda_rng": _device_rng(dev), "cpu_rng": torch.get_rng_state(), "loader": train_loader.state_dict() if per_rank else None}
+    ranks = [None] * world if rank == 0 else None
+    dist.gather_object(mine, ranks, dst=dist.get_global_rank(pg, 0), group=pg)
+    paths = _paths(output_dir, iteration)
+    if rank == 0:
+        for p in paths.values():
+            os.makedirs(os.path.dirname(p), exist_ok=True)
+        torch.save(model.state_dict(), paths["model"])
+        torch.save(optimizer.state_dict(), paths["optimizer"])
+        state = _trainer_state(model, train_loader, iteration, sums, overflowed)
+        state["world"], state["ranks"] = world, ranks
+        torch.save(state, paths["trainer"])
+    dist.barrier(group=pg)
+    return paths
+
+
+def resume(cfg, output_dir, iteration, model, optimizer, train_loader, process_group=None):
     """Load the checkpoint of ``iteration`` into freshly built objects and return the ``resume_iter`` to hand to ``build_scheduler`` and
     ``do_train``.  Build the model with ``resume_iter=iteration`` (its alpha then starts where the reference's would).
 
@@ -219,7 +347,14 @@ def resume(cfg, output_dir, iteration, model, optimizer, train_loader):
     permutation and cursor, the device's and the host's generator state, the loss-scale back-off and the logging sums are restored.  With
     only the reference's files the reference's semantics hold: weights through ``fix_model_state_dict`` with ``strict=False``, alpha from
     the model's constructor, a loader that starts over.  The optimiser file is loaded when it exists (the reference writes it and never
-    reads it back)."""
+    reads it back).
+
+    Data-parallel every rank calls it and loads the files.  At the world size the checkpoint was written at each rank restores ITS device
+    and host generator state (and, outside ``shard_mode="batch"``, its loader state): the continued run is the uninterrupted run.  At
+    another world size a ``shard_mode="batch"`` loader of the same global batch continues the same sample sequence and everything is
+    restored but the generator states (Dropout2d's masks differ from here on), which a warning says; any other change of the world
+    size is a ValueError."""
+    world, rank = _dist(process_group)[2], _dist(process_group)[1]
     paths = _paths(output_dir, iteration)
     sd = fix_model_state_dict(torch.load(paths["model"], map_location="cpu"))
     model.load_state_dict(sd, strict=False)
@@ -235,12 +370,22 @@ def resume(cfg, output_dir, iteration, model, optimizer, train_loader):
     if st["ss_loss_fn"] is not None:
         for k, v in st["ss_loss_fn"].items():
             setattr(model.ss_loss_fn, k, v)
-    if st["loader"] is not None and hasattr(train_loader, "load_state_dict"):
-        train_loader.load_state_dict(st["loader"])
+    saved_world = int(st.get("world", 1))
+    mine = st["ranks"][rank] if saved_world == world and st.get("ranks") is not None else st
+    if saved_world != world:
+        if getattr(train_loader, "shard_mode", None) != "batch" or st["loader"] is None or "global_batch" not in st["loader"]:
+            raise ValueError(f"{paths['trainer']} was written by {saved_world} rank(s) and this run has {world}: only a run whose loaders are "
+                             "in shard_mode='batch' with the same global batch continues on another world size")
+        warnings.warn(f"resuming a checkpoint of {saved_world} rank(s) on {world}: the sample sequence, weights, optimiser state, alpha and "
+                      "loss scale continue; the device and host generator states (Dropout2d masks) are not restored")
+    loader_state = st["loader"] if mine.get("loader") is None else mine["loader"]
+    if loader_state is not None and hasattr(train_loader, "load_state_dict"):
+        train_loader.load_state_dict(loader_state)          # (a global batch other than the saved one raises here)
     dev = _device_of(model)
-    if st["cuda_rng"] is not None and dev.type == "cuda":
-        torch.cuda.set_rng_state(st["cuda_rng"], dev)
-    torch.set_rng_state(st["cpu_rng"])
+    if saved_world == world:
+        if mine["cuda_rng"] is not None and dev.type == "cuda":
+            torch.cuda.set_rng_state(mine["cuda_rng"], dev)
+        torch.set_rng_state(mine["cpu_rng"])
     for k, v in st["loss_scale"].items():
         setattr(model, k, v)
     model._resume_logging = (int(iteration), st["logging"])          # picked up (once) by do_train(resume_iter=iteration)
@@ -249,7 +394,7 @@ def resume(cfg, output_dir, iteration, model, optimizer, train_loader):
 
 # ------------------------------------------------------------------------------------------------------------------ the loop
 def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *, resume_iter=0, log_step=50, save_step=2000, eval_step=2000,
-             output_dir=None, log=print_line, hooks=None):
+             output_dir=None, log=print_line, hooks=None, process_group=None):
     """Train over ``train_loader`` (any iterable of ``(x, hr, mask, k)`` or ``(x, hr, mask, k, sdf)``), iterations counted from
     ``resume_iter + 1``.  Per iteration: set_alpha_phase, model.train(), zero_grad, forward, calc_loss, backward, optimizer.step(),
     scheduler.step().  ``hooks`` (a dict or an object) may carry ``before_step(iteration, model)``, called first in an iteration, and
@@ -259,7 +404,27 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
     losses are window means, ``total`` is ``sr + TASK_LOSS_WEIGHT * seg``, ``overflow_steps`` counts the steps skipped so far because the
     fp16 backward overflowed (``model.last_step_overflowed``, a host flag).  That is the loop's only read-back of device values.  Every
     ``save_step`` iterations the three checkpoint files are written under ``output_dir`` (None: no checkpoints); every ``eval_step``
-    iterations, with an ``eval_loader``, ``validate`` runs with ``model.iter_cnt`` off and its result goes to ``log``."""
+    iterations, with an ``eval_loader``, ``validate`` runs with ``model.iter_cnt`` off and its result goes to ``log``.
+
+    Data-parallel (``torch.distributed`` initialised with world > 1, or CSBSR_FORCE_DIST=1; ``process_group`` None is the default group),
+    every rank calls this with its own model, optimiser and loaders.  At the start a ``GradBucketReducer`` is attached where
+    ``model.reducer`` is None, rank 0's parameters and buffers are broadcast and ``assert_replicas_agree`` checks them.  A step is
+    unchanged (the model's backward drives the reducer; no collective is added).  At a log step the two window sums are SUM-all-reduced
+    and divided by the world size -- with equal shards the mean over the global batch --, ``log`` is called on rank 0 only and
+    ``after_step`` receives the record on every rank; ``overflow_steps`` is common already (the ranks agree on the skip).  Validation and
+    checkpoints: see ``validate`` and ``save_checkpoint``; both are collectives, and a drifted replica raises ReplicaMismatch on every
+    rank before a file is written."""
+    pg, rank, world = _dist(process_group)
+    if pg is not None:
+        dev = _device_of(model)
+        if getattr(model, "reducer", None) is None:
+            model.reducer = GradBucketReducer(pg, side_stream=torch.cuda.Stream(dev) if dev.type == "cuda" else None)
+        if hasattr(model, "_runtime"):
+            model._runtime()          # the parameters move to the device here: broadcast and fingerprint them where they will be trained
+        broadcast_parameters(model, process_group=pg)
+        agree.assert_replicas_agree(replica_tensors(model), pg, what="parameters and buffers after the broadcast")
+        if rank != 0:
+            log = lambda record: None          # noqa: E731  (rank 0 speaks for the run)
     before, after = _hook(hooks, "before_step"), _hook(hooks, "after_step")
     names = {"seg_loss_func": cfg.SOLVER.SEG_LOSS_FUNC, "sr_loss_func": cfg.SOLVER.SR_LOSS_FUNC}
     sums, overflowed = None, 0
@@ -294,6 +459,9 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
 
         record = None
         if iteration % log_step == 0:
+            if pg is not None:          # equal shards: the mean over the ranks is the mean over the global batch
+                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=pg)
+                sums = sums / world
             seg_m, sr_m = (v / log_step for v in sums.tolist())          # the one read-back of the window
             eta = "?" if max_iter is None else str(datetime.timedelta(seconds=int(trained_time / (iteration - resume_iter)
                                                                                   * (max_iter - iteration))))
@@ -307,13 +475,13 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
             tic = time.time()
 
         if output_dir is not None and iteration % save_step == 0:
-            paths = save_checkpoint(output_dir, iteration, model, optimizer, train_loader, sums, overflowed)
+            paths = save_checkpoint(output_dir, iteration, model, optimizer, train_loader, sums, overflowed, process_group=process_group)
             log({"iteration": iteration, "checkpoint": paths["model"], **paths})
 
         if eval_loader is not None and iteration % eval_step == 0:
             model.iter_cnt = False
             try:
-                result = validate(model, eval_loader, iteration)
+                result = validate(model, eval_loader, iteration, process_group=process_group)
             finally:
                 model.iter_cnt = True
             log({"iteration": iteration, **result, **names})

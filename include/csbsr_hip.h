@@ -318,6 +318,26 @@ typedef struct {
 int csbsr_sgd_step(const csbsr_sgd_tensor_t* tensors, const int32_t* block_tensor, const int32_t* block_chunk, int32_t nblocks,
                    double lr, double momentum, double weight_decay, csbsr_stream_t s);
 
+/* Fingerprint of a LIST of device tensors in one launch, with the chunk map of csbsr_adam_step (8192 WORDS per workgroup).  Tensor t is read
+ * as n 32-bit words w_0 .. w_{n-1} (an fp32 element is one word, an int64 element two); all arithmetic is on unsigned 64-bit integers and
+ * wraps modulo 2^64:
+ *     out[t][0] = sum_j w_j              changes with every change of a single word
+ *     out[t][1] = sum_j w_j (j + 1)      changes with every exchange of two unequal words
+ * ``out`` ([T][2], device) must be ZERO on the stream before the call: workgroup partials meet there through 64-bit integer atomic adds,
+ * whose result does not depend on the launch geometry or on the order in which workgroups finish (integer addition is associative).  A
+ * tensor with n == 0 has no workgroup and keeps its zero row.  ``vec`` != 0 states that ``w`` is 16-byte aligned (16-byte loads); a tensor
+ * with vec == 0 is read word by word.  No floating point is involved, so NaN payloads and signed zeros count as the bits they are.
+ *
+ * This is a DRIFT DETECTOR for replicas that should hold identical bits (csbsr_amd/parallel/agree.py), not a hash against an adversary:
+ * two linear sums are trivially forged, and changes that cancel in both sums at once (three or more words) go unnoticed. */
+typedef struct {
+  const uint32_t* w;
+  int64_t n;
+  int32_t vec, _pad;
+} csbsr_fp_tensor_t;
+int csbsr_fingerprint(const csbsr_fp_tensor_t* tensors, const int32_t* block_tensor, const int32_t* block_chunk, int32_t nblocks,
+                      uint64_t* out, csbsr_stream_t s);
+
 int csbsr_axpby(int64_t npix, int32_t c, const void* x, int64_t x_ld, float a, const void* z, int64_t z_ld,
                 float b, void* y, int64_t y_ld, csbsr_stream_t s);
 int csbsr_fill_f16(void* p, int64_t npix, int32_t c, int64_t ld, float v, csbsr_stream_t s);
