@@ -8,6 +8,8 @@ import ctypes as C
 import os
 from collections import namedtuple
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSBSR_LIB") or os.path.join(_HERE, "libcsbsr_hip.so")       # CSBSR_LIB: a variant build (kernel A/B experiments)
 
@@ -255,6 +257,11 @@ def load():
         if h.setter and os.environ.get(h.var):
             getattr(lib, h.setter)(h.setter_parse(os.environ[h.var]))
     return lib
+
+
+def stream(device):
+    """The current HIP stream of ``device`` as the ``csbsr_stream_t`` argument of an entry point."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def call(name, *args):

@@ -31,8 +31,7 @@ class DeviceDegradation:
 
     @property
     def _stream(self):
-        import ctypes as C
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return L.stream(self.device)
 
     def draw_params(self, B):
         """(sigma_x, sigma_y, theta [rad]) per sample with the reference's distributions (blur.py:128,160-167)."""

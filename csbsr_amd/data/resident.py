@@ -15,7 +15,6 @@ reference's RandomResizedCrop (transforms.py:607-622): a window of random area a
 Kernels: csbsr_gather_crop_u8, csbsr_gather_resize_u8 + those of DeviceDegradation.  No CPU / torch fallback: batches exist on a GPU only (the pool, the
 sampler and the table validation also work on ``device="cpu"``, which is what the host-side tests use).
 """
-import ctypes as C
 import glob
 import os
 
@@ -24,7 +23,9 @@ import torch
 
 from .. import _lib as L
 from ..engine import _ptr
+from ..multi_tensor import Staging
 from .degrade import DeviceDegradation
+from .pool import U8Pool, _as_hwc, decode_u8          # noqa: F401  (_as_hwc stays importable from this module)
 
 # cfg.DATASET.DATA_AUGMENTATION of the shipped config/config_csbsr_pspnet.yaml (yaml's bare None arrives as the string "None")
 DEFAULT_AUGMENTATION = (("ConvertFromInts", None), ("RandomMirror", None), ("ToTensor", None), ("RandomVerticalFlip", 0.3), ("RandomCrop", None))
@@ -125,17 +126,6 @@ def split_resized_crop(augmentation):
     return out, rc
 
 
-def _as_hwc(a, channels, what):
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"{what}: expected uint8, got {a.dtype}")
-    if channels == 1 and a.ndim == 2:
-        a = a[:, :, None]
-    if a.ndim != 3 or a.shape[2] != channels or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError(f"{what}: expected H x W x {channels}, got {a.shape}")
-    return a
-
-
 class ResidentDataset:
     """uint8 images (H x W x 3) and masks (H x W or H x W x 1) packed back to back into one contiguous device pool per kind, with an
     int64 byte-offset table and an int32 (H, W) table.  Sizes may differ between samples, not within a pair.  ``subset`` / ``split``
@@ -144,22 +134,17 @@ class ResidentDataset:
     def __init__(self, images, masks, device="cuda:0"):
         if len(images) != len(masks) or len(images) == 0:
             raise ValueError(f"{len(images)} images, {len(masks)} masks")
-        imgs = [_as_hwc(a, 3, f"image {i}") for i, a in enumerate(images)]
-        msks = [_as_hwc(a, 1, f"mask {i}") for i, a in enumerate(masks)]
-        for i, (a, m) in enumerate(zip(imgs, msks)):
-            if a.shape[:2] != m.shape[:2]:
-                raise ValueError(f"sample {i}: image {a.shape[:2]} and mask {m.shape[:2]} differ in size")
         self.device = torch.device(device)
-        self.dims = np.array([a.shape[:2] for a in imgs], dtype=np.int32)                  # host copy: table validation
-        px = self.dims[:, 0].astype(np.int64) * self.dims[:, 1]
-        self.mask_offsets = np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64)
-        self.image_offsets = self.mask_offsets * 3
-        self.image_pool = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(self.device)
-        self.mask_pool = torch.from_numpy(np.concatenate([m.reshape(-1) for m in msks])).to(self.device)
-        self.dims_dev = torch.from_numpy(self.dims).to(self.device)
-        self.image_offsets_dev = torch.from_numpy(self.image_offsets).to(self.device)
-        self.mask_offsets_dev = torch.from_numpy(self.mask_offsets).to(self.device)
-        self.indices = np.arange(len(imgs), dtype=np.int64)                               # pool indices this view holds
+        self.image = U8Pool(images, 3, "image", self.device)
+        self.mask = U8Pool(masks, 1, "mask", self.device)
+        for i, (a, m) in enumerate(zip(self.image.dims, self.mask.dims)):
+            if tuple(a) != tuple(m):
+                raise ValueError(f"sample {i}: image {tuple(int(v) for v in a)} and mask {tuple(int(v) for v in m)} differ in size")
+        # the pools' tensors and tables under this class's names (plain aliases: ``subset`` copies them with __dict__)
+        self.image_pool, self.image_offsets, self.image_offsets_dev = self.image.pool, self.image.offsets, self.image.offsets_dev
+        self.mask_pool, self.mask_offsets, self.mask_offsets_dev = self.mask.pool, self.mask.offsets, self.mask.offsets_dev
+        self.dims, self.dims_dev = self.image.dims, self.image.dims_dev
+        self.indices = np.arange(len(images), dtype=np.int64)                             # pool indices this view holds
 
     @classmethod
     def from_dirs(cls, image_dir, mask_dir, pattern="*.jpg", device="cuda:0"):
@@ -167,7 +152,6 @@ class ResidentDataset:
         taken as PIL decodes them, without mode conversion: an image that does not decode to 8-bit H x W x 3 (grey, palette, RGBA) or
         a mask that does not decode to 8-bit H x W (bilevel, RGB, 16-bit) is an error that names the file.  (A palette mask decodes to
         its 8-bit indices, here as in the reference's ``np.array(Image.open(...))``.)"""
-        from PIL import Image
         names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(image_dir, pattern)))
         if not names:
             raise FileNotFoundError(f"no {pattern} under {image_dir}")
@@ -176,13 +160,8 @@ class ResidentDataset:
             mp = os.path.join(mask_dir, n)
             if not os.path.isfile(mp):
                 raise FileNotFoundError(f"mask {mp} of image {os.path.join(image_dir, n)} is missing")
-            a, m = np.array(Image.open(os.path.join(image_dir, n))), np.array(Image.open(mp))          # as is, like the reference
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError(f"image {os.path.join(image_dir, n)} decodes to {a.dtype} {a.shape}, expected 8-bit RGB (H x W x 3)")
-            if m.dtype != np.uint8 or m.ndim != 2:
-                raise ValueError(f"mask {mp} decodes to {m.dtype} {m.shape}, expected 8-bit single-channel (H x W)")
-            images.append(a)
-            masks.append(m)
+            images.append(decode_u8(os.path.join(image_dir, n), 3, "8-bit RGB (H x W x 3)", what="image "))       # as is, like the reference
+            masks.append(decode_u8(mp, 2, "8-bit single-channel (H x W)", what="mask "))
         ds = cls(images, masks, device=device)
         ds.names = names
         return ds
@@ -214,59 +193,15 @@ class ResidentDataset:
     def sample(self, i):
         """(image H x W x 3, mask H x W x 1) uint8 numpy copies of sample ``i`` of this view."""
         p = int(self.indices[i])
-        H, W = (int(v) for v in self.dims[p])
-        a = self.image_pool[int(self.image_offsets[p]):int(self.image_offsets[p]) + H * W * 3].cpu().numpy().reshape(H, W, 3)
-        m = self.mask_pool[int(self.mask_offsets[p]):int(self.mask_offsets[p]) + H * W].cpu().numpy().reshape(H, W, 1)
-        return a, m
+        return self.image.sample(p), self.mask.sample(p)
 
     def check_selection(self, sel, h, w):
-        """Raise unless every row (index, y0, x0, mirror, vflip) of ``sel`` names a pooled image and an h x w window inside it.  The
-        kernel cannot report a bad row (it clamps), so this runs on the host before every upload."""
-        s = np.asarray(sel)
-        if s.ndim != 2 or s.shape[1] != 5 or s.shape[0] < 1 or not np.issubdtype(s.dtype, np.integer):
-            raise ValueError(f"selection table must be integer [B][5], got {s.dtype} {s.shape}")
-        s = s.astype(np.int64)
-        bad = (s[:, 0] < 0) | (s[:, 0] >= len(self.dims))
-        if bad.any():
-            raise ValueError(f"selection row {int(np.flatnonzero(bad)[0])}: image index {int(s[bad][0, 0])} outside the pool of {len(self.dims)}")
-        d = self.dims[s[:, 0]].astype(np.int64)
-        bad = (s[:, 1] < 0) | (s[:, 1] + h > d[:, 0]) | (s[:, 2] < 0) | (s[:, 2] + w > d[:, 1])
-        if bad.any():
-            r = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"selection row {r}: window y0 {int(s[r, 1])} x0 {int(s[r, 2])} of {h} x {w} leaves image {int(s[r, 0])} "
-                             f"({int(d[r, 0])} x {int(d[r, 1])})")
-        bad = ((s[:, 3] != 0) & (s[:, 3] != 1)) | ((s[:, 4] != 0) & (s[:, 4] != 1))
-        if bad.any():
-            raise ValueError(f"selection row {int(np.flatnonzero(bad)[0])}: mirror / vflip must be 0 or 1")
+        """Raise unless every row (index, y0, x0, mirror, vflip) of ``sel`` names a pooled image and an h x w window inside it."""
+        self.image.check_rows(sel, h, w, "selection")
 
     def check_windows(self, sel, h, w):
-        """Raise unless every row (index, y0, x0, mirror, vflip, hs, ws) of ``sel`` names a pooled image and an hs x ws window inside it
-        that csbsr_gather_resize_u8 may resample to h x w: hs, ws >= 1 and hs <= 8 h, ws <= 8 w (the kernel's tap tables hold 17 taps
-        per axis).  The 7-column sibling of check_selection, for the same reason: the kernel cannot report a bad row."""
-        s = np.asarray(sel)
-        if s.ndim != 2 or s.shape[1] != 7 or s.shape[0] < 1 or not np.issubdtype(s.dtype, np.integer):
-            raise ValueError(f"window table must be integer [B][7], got {s.dtype} {s.shape}")
-        s = s.astype(np.int64)
-        bad = (s[:, 0] < 0) | (s[:, 0] >= len(self.dims))
-        if bad.any():
-            raise ValueError(f"window row {int(np.flatnonzero(bad)[0])}: image index {int(s[bad][0, 0])} outside the pool of {len(self.dims)}")
-        d = self.dims[s[:, 0]].astype(np.int64)
-        bad = (s[:, 5] < 1) | (s[:, 6] < 1)
-        if bad.any():
-            r = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"window row {r}: window size {int(s[r, 5])} x {int(s[r, 6])} must be at least 1 x 1")
-        bad = (s[:, 1] < 0) | (s[:, 1] + s[:, 5] > d[:, 0]) | (s[:, 2] < 0) | (s[:, 2] + s[:, 6] > d[:, 1])
-        if bad.any():
-            r = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"window row {r}: window y0 {int(s[r, 1])} x0 {int(s[r, 2])} of {int(s[r, 5])} x {int(s[r, 6])} leaves image "
-                             f"{int(s[r, 0])} ({int(d[r, 0])} x {int(d[r, 1])})")
-        bad = (s[:, 5] > 8 * h) | (s[:, 6] > 8 * w)
-        if bad.any():
-            r = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"window row {r}: window {int(s[r, 5])} x {int(s[r, 6])} is more than 8 times the output {h} x {w}")
-        bad = ((s[:, 3] != 0) & (s[:, 3] != 1)) | ((s[:, 4] != 0) & (s[:, 4] != 1))
-        if bad.any():
-            raise ValueError(f"window row {int(np.flatnonzero(bad)[0])}: mirror / vflip must be 0 or 1")
+        """The 7-column sibling: rows (..., hs, ws) with an hs x ws window inside the image that may be resampled to h x w."""
+        self.image.check_rows(sel, h, w, "window")
 
     def gather_resized(self, sel_dev, B, h, w, antialias=True):
         """(hr [B,3,h,w], mask [B,1,h,w]) fp32: the hs x ws window of each row of the int32 [B][7] device table ``sel_dev`` (validated by
@@ -274,33 +209,13 @@ class ResidentDataset:
         through the same resample (transforms.py:619-620) and comes out soft."""
         if self.device.type != "cuda":
             raise L.CsbsrHipError("ResidentDataset.gather_resized needs the pool on a GPU: csbsr_amd has no fallback path")
-        if tuple(sel_dev.shape) != (B, 7) or sel_dev.dtype != torch.int32 or not sel_dev.is_contiguous():
-            raise ValueError(f"window table must be a contiguous int32 [{B}][7] tensor, got {sel_dev.dtype} {tuple(sel_dev.shape)}")
-        L.load()
-        hr = torch.empty(B, 3, h, w, dtype=torch.float32, device=self.device)
-        mask = torch.empty(B, 1, h, w, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            L.call("csbsr_gather_resize_u8", _ptr(self.image_pool), _ptr(self.image_offsets_dev), _ptr(self.dims_dev), 3, _ptr(sel_dev),
-                   B, h, w, int(bool(antialias)), _ptr(hr), st)
-            L.call("csbsr_gather_resize_u8", _ptr(self.mask_pool), _ptr(self.mask_offsets_dev), _ptr(self.dims_dev), 1, _ptr(sel_dev),
-                   B, h, w, int(bool(antialias)), _ptr(mask), st)
-        return hr, mask
+        return self.image.gather_resized(sel_dev, B, h, w, antialias), self.mask.gather_resized(sel_dev, B, h, w, antialias)
 
     def gather(self, sel_dev, B, h, w):
         """(hr [B,3,h,w], mask [B,1,h,w]) fp32 = pool bytes / 255 for the int32 [B][5] device table ``sel_dev`` (validated by the caller)."""
         if self.device.type != "cuda":
             raise L.CsbsrHipError("ResidentDataset.gather needs the pool on a GPU: csbsr_amd has no fallback path")
-        L.load()
-        hr = torch.empty(B, 3, h, w, dtype=torch.float32, device=self.device)
-        mask = torch.empty(B, 1, h, w, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            L.call("csbsr_gather_crop_u8", _ptr(self.image_pool), _ptr(self.image_offsets_dev), _ptr(self.dims_dev), 3, _ptr(sel_dev),
-                   B, h, w, _ptr(hr), st)
-            L.call("csbsr_gather_crop_u8", _ptr(self.mask_pool), _ptr(self.mask_offsets_dev), _ptr(self.dims_dev), 1, _ptr(sel_dev),
-                   B, h, w, _ptr(mask), st)
-        return hr, mask
+        return self.image.gather(sel_dev, B, h, w), self.mask.gather(sel_dev, B, h, w)
 
 
 _ROW = 32          # staged bytes per sample: int32 [5] selection row, then fp32 [3] blur parameters (40 with the [7] rows of resized_crop)
@@ -413,7 +328,7 @@ class DeviceTrainLoader:
         self.antialias = bool(antialias)
         self.resize_antialias = True          # of the window's resample: torchvision's default for tensors since 0.17
         self._perm, self._cursor, self._produced, self._resumed = None, 0, 0, False
-        self._ring, self._slot = [None] * _SLOTS, 0
+        self._staging = Staging(self.device, slots=_SLOTS)
 
     @classmethod
     def from_cfg(cls, cfg, dataset, **kw):
@@ -490,24 +405,16 @@ class DeviceTrainLoader:
     def _upload(self, sel, params):
         """sel int32 [B,5] (or [B,7]) + params fp32 [B,3] -> device views, through a pinned staging slot and ONE non-blocking copy.  Before a
         slot is rewritten the host waits for the upload issued from it _SLOTS batches earlier (the pinned bytes must not change under a
-        copy in flight, as in csbsr_amd/optim.py): the only host wait on the device here, and one that blocks only a host running more
+        copy in flight: multi_tensor.Staging): the only host wait on the device here, and one that blocks only a host running more
         than _SLOTS batches ahead of the device."""
         B, cols = sel.shape
         row = 4 * cols + 12          # = _ROW for the [5] rows
-        slot = self._ring[self._slot]
-        if slot is None or slot[0].numel() < B * row:
-            n = max(B, self.batch_size) * row
-            slot = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=self.device), torch.cuda.Event()]
-            self._ring[self._slot] = slot
-        else:
-            slot[2].synchronize()          # (this slot's upload was enqueued _SLOTS batches ago: normally long consumed)
-        self._slot = (self._slot + 1) % _SLOTS
-        host, dev, ev = slot
+        host = self._staging.stage(B * row, self.batch_size * row)
         host[:B * 4 * cols].view(torch.int32).view(B, cols).copy_(sel)
-        host[B * 4 * cols:B * row].view(torch.float32).view(B, 3).copy_(params)
-        dev[:B * row].copy_(host[:B * row], non_blocking=True)
-        ev.record(torch.cuda.current_stream(self.device))
-        return dev[:B * 4 * cols].view(torch.int32).view(B, cols), dev[B * 4 * cols:B * row].view(torch.float32).view(B, 3)
+        host[B * 4 * cols:].view(torch.float32).view(B, 3).copy_(params)
+        dev = self._staging.upload()
+        self._staging.record()
+        return dev[:B * 4 * cols].view(torch.int32).view(B, cols), dev[B * 4 * cols:].view(torch.float32).view(B, 3)
 
     def batch(self, sel, blur_params=None):
         """Decisions -> (x_lr [B,3,h/s,w/s], hr [B,3,h,w], mask [B,1,h,w], kernels [B,1,K,K], sdf [B,1,h,w]).  ``sel`` ([B,5], or [B,7] with

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from .resident_test import _U8Pool
+from .pool import U8Pool, decode_u8
 
 
 def plan_tiles(h, w, ph, pw, halo, scale, index=0):
@@ -68,26 +68,16 @@ class ResidentImageSet:
             raise ValueError(f"{len(images)} images, {len(names)} names")
         self.device = torch.device(device)
         self.names = [str(s) for s in names]
-        self.lr = _U8Pool(images, 3, "LR image", self.device)
+        self.lr = U8Pool(images, 3, "LR image", self.device)
 
     @classmethod
     def from_dir(cls, image_dir, pattern="*.png", device="cuda:0"):
         """Decode ``image_dir/<pattern>`` once with PIL, in sorted order (the reference takes ``Path.glob``'s order).  Files are taken as
         PIL decodes them, without mode conversion; one that does not decode to 8-bit RGB is an error that names the file."""
-        from PIL import Image
         names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(image_dir, pattern)))
         if not names:
             raise FileNotFoundError(f"no {pattern} under {image_dir}")
-        images = []
-        for n in names:
-            p = os.path.join(image_dir, n)
-            try:
-                a = np.array(Image.open(p))
-            except Exception as e:
-                raise ValueError(f"{p} does not decode: {e}") from e
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError(f"{p} decodes to {a.dtype} {a.shape}, expected 8-bit RGB (h x w x 3)")
-            images.append(a)
+        images = [decode_u8(os.path.join(image_dir, n), 3, "8-bit RGB (h x w x 3)", wrap=True) for n in names]
         return cls(images, names, device=device)
 
     def __len__(self):

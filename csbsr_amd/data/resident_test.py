@@ -11,7 +11,6 @@ HBM as fp32.  Iterating touches no host pixel.
 
 No CPU / torch fallback: batches exist on a GPU only (construction and validation also work on ``device="cpu"``, for the host-side tests).
 """
-import ctypes as C
 import glob
 import os
 
@@ -19,34 +18,9 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..engine import _ptr
-from .resident import _as_hwc
+from .pool import U8Pool, _as_hwc, decode_u8
 
-
-class _U8Pool:
-    """uint8 H x W x C arrays packed back to back into one contiguous device pool, with the int64 byte-offset table and the int32 (H, W)
-    table ``csbsr_gather_crop_u8`` reads (the layout of ResidentDataset's pools)."""
-
-    def __init__(self, arrays, channels, what, device):
-        arrays = [_as_hwc(a, channels, f"{what} {i}") for i, a in enumerate(arrays)]
-        self.channels, self.device = channels, torch.device(device)
-        self.dims = np.array([a.shape[:2] for a in arrays], dtype=np.int32)
-        px = self.dims[:, 0].astype(np.int64) * self.dims[:, 1] * channels
-        self.offsets = np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64)
-        self.pool = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(self.device)
-        self.dims_dev = torch.from_numpy(self.dims).to(self.device)
-        self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
-
-    def gather(self, sel_dev, B, h, w):
-        """fp32 [B, channels, h, w] = pool bytes / 255 for the int32 [B][5] device table ``sel_dev`` (rows built from ``dims``)."""
-        if self.device.type != "cuda":
-            raise L.CsbsrHipError("the resident test set needs its pools on a GPU to make a batch: csbsr_amd has no fallback path")
-        out = torch.empty(B, self.channels, h, w, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            L.call("csbsr_gather_crop_u8", _ptr(self.pool), _ptr(self.offsets_dev), _ptr(self.dims_dev), self.channels, _ptr(sel_dev),
-                   B, h, w, _ptr(out), st)
-        return out
+_U8Pool = U8Pool          # (the name this module had it under)
 
 
 def kernel_target(kernel_u8):
@@ -67,9 +41,9 @@ class ResidentTestSet:
             raise ValueError(f"{n} images, {len(masks)} masks, {len(lr_images)} LR images, {len(kernels)} kernels, {len(names)} names")
         self.device = torch.device(device)
         self.names = [str(s) for s in names]
-        self.hr = _U8Pool(hr_images, 3, "image", self.device)
-        self.mask = _U8Pool(masks, 1, "mask", self.device)
-        self.lr = _U8Pool(lr_images, 3, "LR image", self.device)
+        self.hr = U8Pool(hr_images, 3, "image", self.device)
+        self.mask = U8Pool(masks, 1, "mask", self.device)
+        self.lr = U8Pool(lr_images, 3, "LR image", self.device)
         for i in range(n):
             if tuple(self.hr.dims[i]) != tuple(self.mask.dims[i]):
                 raise ValueError(f"{self.names[i]}: image {tuple(self.hr.dims[i])} and mask {tuple(self.mask.dims[i])} differ in size")
@@ -86,7 +60,6 @@ class ResidentTestSet:
         """Decode once with PIL, the reference's layout: names from ``image_dir/*.jpg`` (sorted), the same name under ``mask_dir``, the LR
         image and the kernel at ``<blur_dir>/<blur_name>/lr_images|kernels/<name with jpg -> png>``.  Files are taken as PIL decodes them,
         without mode conversion; one that does not decode to the expected 8-bit layout is an error that names the file."""
-        from PIL import Image
         names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(image_dir, "*.jpg")))
         if not names:
             raise FileNotFoundError(f"no *.jpg under {image_dir}")
@@ -99,10 +72,7 @@ class ResidentTestSet:
                                                                 "8-bit RGB (h x w x 3)", "8-bit single-channel (K x K)"), out):
                 if not os.path.isfile(p):
                     raise FileNotFoundError(f"{p} (of image {paths[0]}) is missing")
-                a = np.array(Image.open(p))
-                if a.dtype != np.uint8 or a.ndim != ndim or (ndim == 3 and a.shape[2] != 3):
-                    raise ValueError(f"{p} decodes to {a.dtype} {a.shape}, expected {what}")
-                dst.append(a)
+                dst.append(decode_u8(p, ndim, what))
         return cls(*out, names, device=device)
 
     def __len__(self):

@@ -138,7 +138,7 @@ class Engine:
 
     @property
     def stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return L.stream(self.device)
 
     def new(self, N, H, W, c, zero=False, split=False):
         f = torch.zeros if zero else torch.empty

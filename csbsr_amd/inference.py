@@ -6,7 +6,6 @@ returns the reference's final report, with the saved images and masks leaving th
 ``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
 of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device."""
 import csv
-import ctypes as C
 import os
 
 import numpy as np
@@ -52,10 +51,6 @@ CLASSIFICATION_IDX = 49                                              # inference
 _SLOTS = 3         # pinned read-back ring: a slot is rewritten three batches after its copies were enqueued, long after it was encoded
 
 
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def stitch_clip_u8(patches, unfold_shape, clip, want_f32=True, want_u8=False):
     """csbsr_stitch_clip_u8 on the model's patch batch [B * nH * nW, C, ph, pw] with the 1-D ``unfold_shape`` of the loader:
     (fp32 [B,C,H,W] or None, uint8 [B,H,W,C] or None) -- JointPatch, the masked clip (``clip``) and ToPILImage's quantisation."""
@@ -73,7 +68,7 @@ def stitch_clip_u8(patches, unfold_shape, clip, want_f32=True, want_u8=False):
     u8 = torch.empty(B, nH * ph, nW * pw, Cc, dtype=torch.uint8, device=p.device) if want_u8 else None
     with torch.cuda.device(p.device):
         L.call("csbsr_stitch_clip_u8", _ptr(p), B, Cc, nH, nW, ph, pw, int(bool(clip)), None if f32 is None else _ptr(f32),
-               None if u8 is None else _ptr(u8), _stream(p))
+               None if u8 is None else _ptr(u8), L.stream(p.device))
     return f32, u8
 
 
@@ -97,7 +92,7 @@ def stitch_tiles_u8(patches, tiles, offsets, dims, clip, out_f32=None, out_u8=No
     N, Cc, PH, PW = p.shape
     with torch.cuda.device(p.device):
         L.call("csbsr_stitch_tiles_u8", _ptr(p), N, Cc, PH, PW, _ptr(tiles), _ptr(offsets), _ptr(dims), int(bool(clip)),
-               None if out_f32 is None else _ptr(out_f32), None if out_u8 is None else _ptr(out_u8), _stream(p))
+               None if out_f32 is None else _ptr(out_f32), None if out_u8 is None else _ptr(out_u8), L.stream(p.device))
 
 
 def threshold_planes_u8(pred, thresholds32):
@@ -110,7 +105,7 @@ def threshold_planes_u8(pred, thresholds32):
     N, S = p.shape[0], th.numel()
     out = torch.empty(N, S, *p.shape[1:], dtype=torch.uint8, device=p.device)
     with torch.cuda.device(p.device):
-        L.call("csbsr_threshold_planes_u8", _ptr(p), _ptr(th), N, p[0].numel(), S, _ptr(out), _stream(p))
+        L.call("csbsr_threshold_planes_u8", _ptr(p), _ptr(th), N, p[0].numel(), S, _ptr(out), L.stream(p.device))
     return out
 
 

@@ -1,6 +1,6 @@
 """Adam on the device, hand-written: the optimiser step of the reference's training loop -- ``torch.optim.Adam(params, lr, betas=(0.9, 0.999),
 eps=1e-8)``, /root/reference/train.py:91, no weight decay, no amsgrad -- as ONE multi-tensor HIP launch per parameter group
-(``csbsr_adam_step``, csrc/elementwise.hip) instead of torch's foreach kernels (52 launches, 3 ms per config-2 step; the last vendor /
+(``csbsr_adam_step``, csrc/multi_tensor.hip) instead of torch's foreach kernels (52 launches, 3 ms per config-2 step; the last vendor /
 torch arithmetic on the timed path besides a few [B, 441] einsums).
 
 Drop-in for ``torch.optim.Adam`` in that configuration: a ``torch.optim.Optimizer`` subclass (``LambdaLR`` and the reference's warm-up schedulers
@@ -10,18 +10,18 @@ training phases and an overflowed backward rely on), the same arithmetic operati
 tests/test_elementwise_gpu.py::test_adam_step_matches_torch).  fp32 parameters on the device only; anything else raises.
 
 ``SGD`` is the same for ``torch.optim.SGD(params, lr, momentum=0.9, weight_decay=5e-4)`` (train.py:93, MODEL.OPTIMIZER "SGD"): one
-``csbsr_sgd_step`` launch per group over the same chunk map and staging table, torch's state key ``momentum_buffer``, torch's skip rule, and
-a ``state_dict()`` that ``torch.optim.SGD`` loads and steps from (tests/test_trainer_gpu.py::test_sgd_step_matches_torch).
+``csbsr_sgd_step`` launch per group over the same chunk map and staging table (csbsr_amd/multi_tensor.py), torch's state key
+``momentum_buffer``, torch's skip rule, and a ``state_dict()`` that ``torch.optim.SGD`` loads and steps from
+(tests/test_trainer_gpu.py::test_sgd_step_matches_torch).
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import multi_tensor as MT
 
-_CHUNK = 8192
 _DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"), ("bc2_sqrt", "<f4")])
 assert _DT.itemsize == 48
 _SGD_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("vec", "<i4"), ("pad", "<i4")])
@@ -29,45 +29,19 @@ assert _SGD_DT.itemsize == 40
 
 
 class _MultiTensor(torch.optim.Optimizer):
-    """What the one-launch optimisers share: the chunk map per set of tensor sizes and the pinned staging of the per-step table."""
+    """What the one-launch optimisers share: one pinned staging of the per-step table per parameter group (csbsr_amd/multi_tensor.py)."""
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         L.load()
-        self._maps = {}          # tuple of tensor sizes -> (block_tensor, block_chunk) device int32 tensors
-        self._host = {}          # group index -> pinned staging for its per-step table (+ the event that says the last upload has been read)
-
-    def _block_maps(self, sizes, device):
-        key = (tuple(sizes), str(device))
-        mp = self._maps.get(key)
-        if mp is None:
-            bt, bc = [], []
-            for i, n in enumerate(sizes):
-                k = (n + _CHUNK - 1) // _CHUNK
-                bt.append(np.full(k, i, dtype=np.int32))
-                bc.append(np.arange(k, dtype=np.int32))
-            mp = (torch.from_numpy(np.concatenate(bt)).to(device), torch.from_numpy(np.concatenate(bc)).to(device))
-            self._maps[key] = mp
-        return mp
+        self._host = {}          # group index -> Staging of its per-step table
 
     def _launch(self, name, slot, tab, ps, dev, *scalars):
         """Upload ``tab`` (one row per tensor of ``ps``, the stepped tensors of group ``slot``) and run entry point ``name`` over the chunk
         map of ``ps`` on the current stream."""
-        bt, bc = self._block_maps([p.numel() for p in ps], dev)
-        raw = torch.from_numpy(tab.view(np.uint8))
-        host = self._host.get(slot)
-        if host is not None and host[0].numel() >= raw.numel() and host[1].device == dev:
-            host[2].synchronize()          # (the previous step's upload was consumed long ago: returns at once)
-        else:
-            n = max(raw.numel(), 4096)
-            host = self._host[slot] = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=dev),
-                                       torch.cuda.Event()]
-        host[0][:raw.numel()].copy_(raw)
-        with torch.cuda.device(dev):
-            host[1][:raw.numel()].copy_(host[0][:raw.numel()], non_blocking=True)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call(name, C.c_void_p(host[1].data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(bc.data_ptr()), int(bt.numel()), *scalars, stream)
-            host[2].record(torch.cuda.current_stream(dev))
+        if slot not in self._host or self._host[slot].device != dev:
+            self._host[slot] = MT.Staging(dev)
+        MT.launch(name, self._host[slot], tab.view(np.uint8), [p.numel() for p in ps], dev, *scalars)
 
 
 def _check(p, g, dev, who):

@@ -1,7 +1,7 @@
 """Do the replicas of a data-parallel run still hold the same bits?
 
-Every rank fingerprints its tensors on its own device -- ONE launch of ``csbsr_fingerprint`` (csrc/elementwise.hip) over the chunk map and
-the pinned staging table of the one-launch optimisers (csbsr_amd/optim.py) -- and the ranks compare the [T, 2] tables with a MIN and a MAX
+Every rank fingerprints its tensors on its own device -- ONE launch of ``csbsr_fingerprint`` (csrc/multi_tensor.hip) over the chunk map and
+the pinned staging table of the one-launch optimisers (csbsr_amd/multi_tensor.py) -- and the ranks compare the [T, 2] tables with a MIN and a MAX
 all-reduce: a few KB on the wire where gathering the tensors themselves would be 357 MB per rank.  A row whose minimum and maximum differ
 names a tensor that is not the same on every rank; every rank computes the same list.
 
@@ -20,13 +20,12 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib as L
+from .. import multi_tensor as MT
 
-_CHUNK = 8192          # 32-bit words per workgroup (the optimisers' chunk)
 _FP_DT = np.dtype([("w", "<u8"), ("n", "<i8"), ("vec", "<i4"), ("pad", "<i4")])
 assert _FP_DT.itemsize == 24
 
-_maps = {}          # (word counts, device) -> (block_tensor, block_chunk) device int32 tensors
-_host = {}          # device -> [pinned staging, device table, event after the last launch that read it]
+_host = {}          # device -> Staging of the table
 
 
 class ReplicaMismatch(RuntimeError):
@@ -53,16 +52,6 @@ def _words(t, dev):
     return nbytes // 4
 
 
-def _block_maps(sizes, dev):
-    key = (tuple(sizes), str(dev))
-    mp = _maps.get(key)
-    if mp is None:
-        bt = [np.full((n + _CHUNK - 1) // _CHUNK, i, dtype=np.int32) for i, n in enumerate(sizes)]
-        bc = [np.arange((n + _CHUNK - 1) // _CHUNK, dtype=np.int32) for n in sizes]
-        mp = _maps[key] = (torch.from_numpy(np.concatenate(bt)).to(dev), torch.from_numpy(np.concatenate(bc)).to(dev))
-    return mp
-
-
 def fingerprint(tensors):
     """[T, 2] int64 on the tensors' device (the unsigned 64-bit sums, bit for bit; nothing is read back): row t is the fingerprint of
     ``tensors[t]``.  Accepted: tensors on one GPU, contiguous, of a byte length that is a multiple of 4 (fp32 parameters and buffers,
@@ -80,21 +69,8 @@ def fingerprint(tensors):
         out = torch.zeros(len(tensors), 2, dtype=torch.int64, device=dev)          # (zeroed on the stream the kernel adds on)
         if not any(sizes):
             return out
-        bt, bc = _block_maps(sizes, dev)
-        raw = torch.from_numpy(tab.view(np.uint8))
-        host = _host.get(str(dev))
-        if host is not None and host[0].numel() >= raw.numel():
-            host[2].synchronize()          # the pinned bytes must not change under the previous call's copy
-        else:
-            n = max(raw.numel(), 4096)
-            host = _host[str(dev)] = [torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.uint8, device=dev),
-                                      torch.cuda.Event()]
-        host[0][:raw.numel()].copy_(raw)
-        host[1][:raw.numel()].copy_(host[0][:raw.numel()], non_blocking=True)
-        stream = torch.cuda.current_stream(dev)
-        L.call("csbsr_fingerprint", C.c_void_p(host[1].data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(bc.data_ptr()), int(bt.numel()),
-               C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
-        host[2].record(stream)
+        staging = _host.setdefault(str(dev), MT.Staging(dev))
+        MT.launch("csbsr_fingerprint", staging, tab.view(np.uint8), sizes, dev, C.c_void_p(out.data_ptr()))
     return out
 
 

@@ -2,17 +2,12 @@
 model/utils/estimate_metrics.py:64-191 and model/engine/inference.py:50-53,111-119, as single-pass HIP kernels
 (csbsr_psnr_ssim, csbsr_iou_sweep) instead of five depthwise convolutions per SSIM and a [B,99,H,W] broadcast + a host numpy
 reduction per batch.  Same class names / call conventions as the reference; results come back as numpy arrays like there."""
-import ctypes as C
 
 import numpy as np
 import torch
 
 from .. import _lib as L
 from ..engine import _ptr, _reduction_scratch
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _dev32(t, like=None):
@@ -29,7 +24,7 @@ def psnr_ssim(img1, img2):
     _reduction_scratch(a.device)         # the sums are an order-fixed fold of per-workgroup partial rows (csrc/common.h)
     sums = torch.zeros(B, 2, dtype=torch.float32, device=a.device)
     ps, ss = torch.empty(B, dtype=torch.float32, device=a.device), torch.empty(B, dtype=torch.float32, device=a.device)
-    L.call("csbsr_psnr_ssim", _ptr(a), _ptr(b), B, Cc, H, W, _ptr(sums), _ptr(ps), _ptr(ss), _stream(a))
+    L.call("csbsr_psnr_ssim", _ptr(a), _ptr(b), B, Cc, H, W, _ptr(sums), _ptr(ps), _ptr(ss), L.stream(a.device))
     return ps, ss
 
 
@@ -67,7 +62,7 @@ def iou_sweep(segment_preds, masks, thresholds, smooth=1e-5):
     T = th.numel()
     hist = torch.zeros(B, 2, T + 1, dtype=torch.int32, device=p.device)
     out = torch.empty(B, T, dtype=torch.float32, device=p.device)
-    L.call("csbsr_iou_sweep", _ptr(p), _ptr(m), _ptr(th), B, hw, T, float(smooth), _ptr(hist), _ptr(out), None, None, _stream(p))
+    L.call("csbsr_iou_sweep", _ptr(p), _ptr(m), _ptr(th), B, hw, T, float(smooth), _ptr(hist), _ptr(out), None, None, L.stream(p.device))
     return out
 
 
@@ -177,7 +172,7 @@ def surface_distance_sweep(segment_preds, masks, thresholds, percent=50.0, works
     T = th.numel()
     dev = p.device
     th = th.to(dev)
-    st = _stream(p)
+    st = L.stream(p.device)
     ncorner = (H + 1) * (W + 1)
     i32, u8 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.uint8, device=dev)
     lvl, gt = torch.empty(H * W, **u8), torch.empty(H * W, **u8)

@@ -94,6 +94,22 @@ def test_batch_equals_device_degradation_on_the_gathered_tensors():
     assert all(t.device == torch.device(DEV) and t.dtype == torch.float32 for t in (x, hr, mask, k, sdf))
 
 
+def test_staging_ring_reuse_and_growth():
+    """Six forced tables of 2, 2, 5, 2, 2, 2 rows through a loader of batch_size 2: more calls than the staging ring has slots, the third
+    outgrows its slot, and nothing waits for the device in between.  Every batch is the NumPy restatement on its own rows, bit for bit."""
+    from csbsr_amd.data.resident import ResidentDataset, DeviceTrainLoader, _SLOTS
+    h, w = 16, 24
+    rng = np.random.default_rng(21)
+    images, masks = RC.random_pairs(rng, [(20, 30)] * 12)
+    ld = DeviceTrainLoader(ResidentDataset(images, masks, device=DEV), (h, w), 4, batch_size=2, blur=False, seed=0)
+    tables = [RC.random_selection(rng, ld.dataset.dims, B, h, w) for B in (2, 2, 5, 2, 2, 2)]
+    assert len(tables) > _SLOTS
+    got = [ld.batch(torch.from_numpy(sel))[1:3] for sel in tables]
+    for i, (sel, (hr, mask)) in enumerate(zip(tables, got)):
+        assert torch.equal(hr.cpu(), torch.from_numpy(RC.gather_numpy(images, sel, h, w))), f"hr of call {i}"
+        assert torch.equal(mask.cpu(), torch.from_numpy(RC.gather_numpy(masks, sel, h, w))), f"mask of call {i}"
+
+
 def test_blur_false_gives_a_delta_kernel_and_the_unblurred_lr():
     from csbsr_amd import _lib as L
     from csbsr_amd.data.degrade import DeviceDegradation

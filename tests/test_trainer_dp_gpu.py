@@ -58,6 +58,22 @@ def test_fingerprint_equals_the_numpy_restatement_bit_for_bit(fp_list):
     assert torch.equal(agree.fingerprint(dev[::-1]), got.flip(0))
 
 
+def test_fingerprint_table_staging_reuse_and_growth(fp_list):
+    """The pinned table of agree.fingerprint through its life: allocated for 3 rows (72 B in the 4096 B minimum), reused for 40 rows
+    (960 B) and for the first 3 again, then outgrown by 180 rows (4320 B).  Every table is the numpy restatement, bit for bit."""
+    from csbsr_amd.parallel import agree
+    _, dev, host = fp_list
+    agree._host.pop(DEV, None)          # whatever earlier tests left: the sequence starts from no staging
+    rng = np.random.default_rng(13)
+    ones = [rng.integers(0, 2 ** 32, size=1, dtype=np.uint64).astype("<u4").view(np.float32) for _ in range(180)]
+    pick = [i % len(dev) for i in range(40)]
+    lists = [(dev[:3], host[:3]), ([dev[i] for i in pick], [host[i] for i in pick]), (dev[:3], host[:3]),
+             ([torch.from_numpy(a).to(DEV) for a in ones], ones)]
+    got = [agree.fingerprint(d) for d, _ in lists]
+    for k, (g, (_, h)) in enumerate(zip(got, lists)):
+        assert torch.equal(g.cpu(), torch.from_numpy(FC.fingerprint_numpy(h))), f"call {k}"
+
+
 def test_fingerprint_sees_a_flipped_bit_and_an_exchange(fp_list):
     from csbsr_amd.parallel import agree
     names, dev, _ = fp_list
