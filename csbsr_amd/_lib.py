@@ -146,6 +146,7 @@ SIGNATURES = {
     "csbsr_bilinear32_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_bilinear32_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_bicubic_up_add": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "csbsr_aa_bicubic_up": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_aa_bicubic_down_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "csbsr_aa_bicubic_down_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_blur_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]),

@@ -658,6 +658,138 @@ extern "C" int csbsr_aa_bicubic_down_bwd(const float* dy, float* dx, int32_t acc
   return 0;
 }
 
+// Bicubic up-scale by an integer factor s (a multiple of 4) as torchvision's Resize(BICUBIC) computes it for a float tensor:
+//   antialias = 1: F.interpolate(bicubic, antialias=True) -- Keys' cubic with A = -0.5, the taps [int(c - 1.5), int(c + 2.5)) CUT to the
+//                  image and the remaining weights renormalised (c = (o + 0.5) / s);
+//   antialias = 0: F.interpolate(bicubic) -- A = -0.75, four taps whose INDICES are clamped to the image (csbsr_bicubic_up_add's rule).
+// Both are separable, y = M_y x M_x^T, and for s % 4 == 0 the four outputs 4q .. 4q + 3 of an axis lie in ONE input cell g = 4q / s, so all
+// their taps fall into the five input samples g - 2 .. g + 2.  A weight row is therefore stored relative to that window (zeros where a tap
+// is cut; a clamped tap is added onto the window slot of the sample it clamps to), and a thread turns one clamped 5 x 5 input window into a
+// 4 x 4 output block: 25 loads through L1 / L2, 100 + 80 FMAs, four 16-byte stores.  A workgroup covers 256 x 16 outputs; its 256 + 16 weight
+// rows are built once in LDS (component-major, so the four rows a lane needs are one conflict-free ds_read_b128 per window slot), which
+// keeps the border rules out of the inner loop.  A wave stores 1 KiB contiguous per output row.  No atomics: bit-reproducible.
+__device__ __forceinline__ void up_weights5(int o, int n, int s, int antialias, float w[5]) {
+  const int base = o / s - 2;
+  const float c = (o + 0.5f) / (float)s;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) w[i] = 0.f;
+  if (antialias) {
+    int lo = (int)(c - 1.5f); if (lo < 0) lo = 0;
+    int hi = (int)(c + 2.5f); if (hi > n) hi = n;
+    float wj[4], tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { wj[k] = lo + k < hi ? aa_filter(lo + k - c + 0.5f) : 0.f; tot += wj[k]; }
+    const float inv = 1.f / tot;
+    const int d = lo - base;        // 0 .. 2, and d + (hi - lo) <= 5
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int i = 0; i < 5; ++i) if (i == d + k && lo + k < hi) w[i] = wj[k] * inv;
+  } else {
+    const float A = -0.75f;
+    const float sx = c - 0.5f, fl = floorf(sx), t = sx - fl;
+    const int st = (int)fl - 1;
+    const float w4[4] = {cubic2(t + 1.f, A), cubic1(t, A), cubic1(1.f - t, A), cubic2(2.f - t, A)};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      int j = st + k; j = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);
+      const int p = j - base;       // 0 .. 4
+#pragma unroll
+      for (int i = 0; i < 5; ++i) if (i == p) w[i] += w4[k];
+    }
+  }
+}
+#define UP_TW 256
+#define UP_TH 16
+__global__ __launch_bounds__(256) void aa_bicubic_up_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int s, int antialias,
+                                                            int clip) {
+  __shared__ float4 wxs[5][UP_TW / 4];      // [window slot][thread column]: the slot's weight of the thread's four output columns
+  __shared__ float4 wys[5][UP_TH / 4];
+  const int OH = H * s, OW = W * s;
+  const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+  const int bx0 = blockIdx.x * UP_TW, by0 = blockIdx.y * UP_TH;
+  {
+    float w[5];
+    const int ox = bx0 + tid;
+    if (ox < OW) up_weights5(ox, W, s, antialias, w);
+    else { for (int i = 0; i < 5; ++i) w[i] = 0.f; }
+    float* wx = reinterpret_cast<float*>(wxs);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) wx[i * UP_TW + tid] = w[i];
+    if (tid < UP_TH) {
+      const int oy = by0 + tid;
+      if (oy < OH) up_weights5(oy, H, s, antialias, w);
+      else { for (int i = 0; i < 5; ++i) w[i] = 0.f; }
+      float* wy = reinterpret_cast<float*>(wys);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) wy[i * UP_TH + tid] = w[i];
+    }
+  }
+  __syncthreads();
+  const int ox0 = bx0 + tx * 4, oy0 = by0 + ty * 4;
+  if (ox0 >= OW || oy0 >= OH) return;       // OW and OH are multiples of 4: a thread's block is inside or outside as a whole
+  const float* xp = x + (long)blockIdx.z * H * W;
+  const int gx = ox0 / s - 2, gy = oy0 / s - 2;
+  int cx[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) { int v = gx + j; cx[j] = v < 0 ? 0 : (v > W - 1 ? W - 1 : v); }
+  float wxv[5][4], wyv[5][4];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const float4 a = wxs[i][tx], b = wys[i][ty];
+    wxv[i][0] = a.x; wxv[i][1] = a.y; wxv[i][2] = a.z; wxv[i][3] = a.w;
+    wyv[i][0] = b.x; wyv[i][1] = b.y; wyv[i][2] = b.z; wyv[i][3] = b.w;
+  }
+  float acc[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[r][q] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    int yy = gy + i; yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+    const float* row = xp + (long)yy * W;
+    float v[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) v[j] = row[cx[j]];
+    float hsum[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float h = 0.f;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) h += wxv[j][q] * v[j];
+      hsum[q] = h;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[r][q] += wyv[i][r] * hsum[q];
+  }
+  float* yp = y + ((long)blockIdx.z * OH + oy0) * OW + ox0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float4 o = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    if (clip) {
+      o.x = fminf(fmaxf(o.x, 0.f), 1.f); o.y = fminf(fmaxf(o.y, 0.f), 1.f);
+      o.z = fminf(fmaxf(o.z, 0.f), 1.f); o.w = fminf(fmaxf(o.w, 0.f), 1.f);
+    }
+    *reinterpret_cast<float4*>(yp + (long)r * OW) = o;
+  }
+}
+extern "C" int csbsr_aa_bicubic_up(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t scale, int32_t antialias,
+                                   int32_t clip, csbsr_stream_t s) {
+  CSBSR_CHECK(x && y && planes >= 1 && H >= 1 && W >= 1, "aa_bicubic_up: bad args");
+  CSBSR_CHECK(scale >= 4 && scale % 4 == 0, "aa_bicubic_up: scale %d (a multiple of 4: the x4 / x8 paths)", scale);
+  CSBSR_CHECK(((uintptr_t)y & 15) == 0, "aa_bicubic_up: the output is not 16-byte aligned");
+  const long OH = (long)H * scale, OW = (long)W * scale;
+  const long gy = (OH + UP_TH - 1) / UP_TH;
+  CSBSR_CHECK(OH * OW < (1l << 31) && planes <= 65535 && gy <= 65535, "aa_bicubic_up: %d planes of %ld x %ld exceed the grid", planes, OH, OW);
+  hipLaunchKernelGGL(aa_bicubic_up_kernel, dim3((unsigned)((OW + UP_TW - 1) / UP_TW), (unsigned)gy, (unsigned)planes), dim3(256), 0, ST(s), x, y,
+                     H, W, scale, antialias, clip);
+  CSBSR_LAUNCH_CHECK("csbsr_aa_bicubic_up");
+  return 0;
+}
+
 // fp32 single-plane bilinear resize (aux head, align_corners=True: pspnet.py:122) and its adjoint
 __device__ __forceinline__ void bil_src32(int o, int in, int out, int align, int& i0, int& i1, float& w1) {
   float src;

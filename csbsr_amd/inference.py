@@ -19,6 +19,15 @@ from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
 
+def _kernel_for_psnr(model, kernel_preds, kernel_targets):
+    """The kernel estimate the kernel-PSNR column is taken on.  A MODEL.SR == "bicubic" model has none: its ``kernel_preds`` are zeros
+    of the DUMMY kernel's shape, and the column is the PSNR of a zero kernel of the target's shape -- what the reference computes whenever
+    its shapes allow."""
+    if getattr(model, "sr_model", None) == "bicubic" and kernel_preds.shape != kernel_targets.shape:
+        return torch.zeros_like(kernel_targets, dtype=kernel_preds.dtype)
+    return kernel_preds
+
+
 @torch.no_grad()
 def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, masks, kernel_targets, ksize, thresholds=THRESHOLDS,
                    surface_distance=False):
@@ -36,7 +45,7 @@ def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, 
     sr_preds = sr_preds.clamp(0, 1)
     kernel_preds = kernel_preds.clamp(0, 1)
     ps, ss = psnr_ssim(sr_preds, sr_targets)
-    kps, _ = psnr_ssim(kernel_preds, kernel_targets)
+    kps, _ = psnr_ssim(_kernel_for_psnr(model, kernel_preds, kernel_targets), kernel_targets)
     iou = iou_sweep(segment_preds, masks, thresholds)
     out = dict(sr_preds=sr_preds, segment_preds=segment_preds, kernel_preds=kernel_preds, psnr=ps.cpu().numpy(), ssim=ss.cpu().numpy(),
                kernel_psnr=kps.cpu().numpy(), iou=iou.cpu().numpy())
@@ -249,7 +258,7 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
         segment_preds, seg_u8 = stitch_clip_u8(seg_p, seg_shape, clip=False, want_u8=saver is not None)
         kernel_preds = kernel_preds.clamp(0, 1)
         ps, ss = psnr_ssim(sr_preds, sr_targets)
-        kps, _ = psnr_ssim(kernel_preds, kernel_targets)
+        kps, _ = psnr_ssim(_kernel_for_psnr(model, kernel_preds, kernel_targets), kernel_targets)
         acc["psnr"].append(ps)
         acc["ssim"].append(ss)
         acc["kernel_psnr"].append(kps)

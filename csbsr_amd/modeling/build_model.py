@@ -99,9 +99,15 @@ def _init_reference_style(name, t, gen):
 class _JointBase(nn.Module):
     def __init__(self, cfg, antialias=True, device="cuda:0", seed=None):
         super().__init__()
-        if cfg.MODEL.SR != "KBPN" or cfg.MODEL.DETECTOR_TYPE not in ("PSPNet", "PSPNet_BlurSkip", "HRNet_OCR"):
-            raise NotImplementedError(f"csbsr_amd builds KBPN + PSPNet / PSPNet_BlurSkip / HRNet_OCR; got SR={cfg.MODEL.SR} "
-                                      f"DETECTOR_TYPE={cfg.MODEL.DETECTOR_TYPE}")
+        # MODEL.SR="bicubic" (build_model.py:69-73, 90-91): the paper's lower-bound row, the detector on the bicubically up-scaled LR image.
+        # PSPNet_BlurSkip is not built with it: its SFT layers are fed KBPN's kernel estimate, which this model does not have
+        self.bicubic = cfg.MODEL.SR == "bicubic"
+        if cfg.MODEL.SR not in ("KBPN", "bicubic") or cfg.MODEL.DETECTOR_TYPE not in ("PSPNet", "PSPNet_BlurSkip", "HRNet_OCR") or \
+                (self.bicubic and cfg.MODEL.DETECTOR_TYPE == "PSPNet_BlurSkip"):
+            raise NotImplementedError(f"csbsr_amd builds KBPN + PSPNet / PSPNet_BlurSkip / HRNet_OCR and bicubic + PSPNet / HRNet_OCR; got "
+                                      f"SR={cfg.MODEL.SR} DETECTOR_TYPE={cfg.MODEL.DETECTOR_TYPE}")
+        if self.bicubic and cfg.MODEL.SCALE_FACTOR % 4:      # csbsr_aa_bicubic_up stores four outputs of one input cell per lane
+            raise NotImplementedError(f"MODEL.SR='bicubic' with SCALE_FACTOR={cfg.MODEL.SCALE_FACTOR}: a multiple of 4")
         if cfg.MODEL.SUM_LR_ERROR_POS not in ("HR", "LR"):      # kbpn.py:174-187: the reference's forward handles exactly these two
             raise NotImplementedError(f"MODEL.SUM_LR_ERROR_POS={cfg.MODEL.SUM_LR_ERROR_POS!r}: 'HR' or 'LR'")
         if cfg.MODEL.NUM_CLASSES != 1:      # build_model.py:209: every kernel of this path assumes the 1-class crack map
@@ -120,7 +126,8 @@ class _JointBase(nn.Module):
                                     zero_pad_kernel=self.pc.zero_pad_kernel)
         # registration order = reference state_dict order: segmentation_model.* then sr_model.*
         self.segmentation_model = _ParamGroup(shapes, "segmentation_model")
-        self.sr_model = _ParamGroup(shapes, "sr_model")
+        # (bicubic: the reference's ``sr_model`` is this string and its state_dict / parameters() hold the detector alone)
+        self.sr_model = "bicubic" if self.bicubic else _ParamGroup(shapes, "sr_model")
         gen = torch.Generator().manual_seed(cfg.SEED if seed is None else seed)
         for full, t in self._named_full():
             if t.is_floating_point() and not full.endswith(("running_mean", "running_var")):
@@ -176,7 +183,7 @@ class _JointBase(nn.Module):
 
     # ---- naming: state_dict keys are the reference's dotted names
     def _named_full(self):
-        for grp in ("segmentation_model", "sr_model"):
+        for grp in ("segmentation_model",) if self.bicubic else ("segmentation_model", "sr_model"):
             for local, t in getattr(self, grp).named_local():
                 yield f"{grp}.{local}", t
 
@@ -207,7 +214,7 @@ class _JointBase(nn.Module):
             self.to(self._device)
             eng = Engine(self._device)
             P = {k: (v.data if isinstance(v, nn.Parameter) else v) for k, v in self._named_full()}
-            self._rt = {"eng": eng, "P": P, "kbpn": KBPN(eng, P, self.pc), "psp": HRNetOCR(eng, P) if self.seg_model_name == "HRNet_OCR"
+            self._rt = {"eng": eng, "P": P, "kbpn": None if self.bicubic else KBPN(eng, P, self.pc), "psp": HRNetOCR(eng, P) if self.seg_model_name == "HRNet_OCR"
                         else PSPNet(eng, P, blur_dim=self.pc.ksize_out ** 2 if self.blur_skip else None)}
             self._make_grad_buckets()
         if self.detector_precision not in ("fp16", "split"):
@@ -254,7 +261,8 @@ class _JointBase(nn.Module):
 
     def _invalidate(self):
         rt = self._rt
-        rt["kbpn"].invalidate()
+        if rt["kbpn"] is not None:
+            rt["kbpn"].invalidate()
         rt["psp"].invalidate()
         rt["eng"].new_step()            # (master weights may have been stepped: every PReLU slope probe may issue one new asynchronous read)
 
@@ -284,6 +292,15 @@ class _JointBase(nn.Module):
             mean = invstd = None
         return eng.nchw32_to_fm(sr32, mean=mean, invstd=invstd, split=self.detector_precision == "split"), mean, invstd
 
+    def _bicubic_up(self, x, clip):
+        """MODEL.SR="bicubic": transforms.Resize(size * scale, BICUBIC) of the LR batch (build_model.py:69-73), clipped to [0, 1] in the
+        same pass when asked (clip_sr)."""
+        eng, pc = self._rt["eng"], self.pc
+        B, Cc, h, w = x.shape
+        sr32 = eng.f32(B, Cc, h * pc.scale, w * pc.scale, zero=False)
+        L.call("csbsr_aa_bicubic_up", _ptr(x), _ptr(sr32), B * Cc, h, w, pc.scale, int(pc.antialias), int(bool(clip)), eng.stream)
+        return sr32
+
 
 class _JointFn(torch.autograd.Function):
     """(segment_loss[B], sr_loss[B]) = f(parameters); backward = the HIP backward pass."""
@@ -303,10 +320,31 @@ class _JointFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+class _SegFn(torch.autograd.Function):
+    """segment_loss[B] = f(detector parameters) of the MODEL.SR="bicubic" model; backward = the detector half of the HIP backward pass."""
+
+    @staticmethod
+    def forward(ctx, model, st, seg_loss, *params):
+        ctx.model, ctx.st = model, st
+        ctx.set_materialize_grads(False)
+        return seg_loss.clone()
+
+    @staticmethod
+    def backward(ctx, dseg):
+        st, ctx.st = ctx.st, None
+        if st is None:
+            raise RuntimeError("csbsr_amd: backward called twice on the same forward (activations are freed by the first backward)")
+        grads = ctx.model._hip_backward(st, dseg, None)
+        return (None, None, None) + tuple(grads)
+
+
 class JointModelWithLoss(_JointBase):
     def __init__(self, cfg, num_train_ds, resume_iter, sr_transforms=None, antialias=True, device="cuda:0", seed=None):
         super().__init__(cfg, antialias, device, seed)
-        if cfg.SOLVER.SEG_LOSS_FUNC != "BoundaryCombo" or cfg.SOLVER.SR_LOSS_FUNC != "KBPN":
+        # bicubic: calc_sr_loss returns None before it looks at the loss function (build_model.py:163-166), so the keys that only shape
+        # KBPN or the SR loss have no effect, as in the reference (the list: DESIGN.md section 1.5); _JointBase's refusals of values no model
+        # of this build takes (SUM_LR_ERROR_POS, NUM_CLASSES, SR_SEG_INV, JOINT_LEARNING) hold for this model too
+        if cfg.SOLVER.SEG_LOSS_FUNC != "BoundaryCombo" or (cfg.SOLVER.SR_LOSS_FUNC != "KBPN" and not self.bicubic):
             raise NotImplementedError("csbsr_amd builds SEG_LOSS_FUNC=BoundaryCombo with SR_LOSS_FUNC=KBPN")
         if cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SS_AMP != 0 or cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0 or cfg.SOLVER.INTERM_SSLOSSWEGHT4SR:
             raise NotImplementedError("oriented loss weights other than SEG_FAIL_ORIENTED_WEIGHT4SR are not built")
@@ -328,6 +366,14 @@ class JointModelWithLoss(_JointBase):
         """``segment_sdf`` (optional, not in the reference's signature): the signed distance map of ``segment_targets`` already on the
         device -- csbsr_amd.data.degrade.DeviceDegradation computes it with the batch -- so the loss does not recompute it."""
         rt = self._runtime()
+        if self.bicubic:
+            # forward_sr's bicubic branch: sr_preds is the UNCLIPPED up-scaled input, kernel_preds zeros of the target's shape, sr_loss None;
+            # the detector and its loss are the kernels of the joint model's detector half on the same bytes
+            self._invalidate()
+            x, mask, kgt = self._mount(x), self._mount(segment_targets), self._mount(kernel_targets)
+            self._n_res = 0
+            return self._detector_and_losses(iter, x, None, mask, kgt, self._bicubic_up(x, clip=False), None, None, x.shape[0],
+                                             sdf=self._mount(segment_sdf), sr_terms=False)
         eng, kbpn, psp, pc = rt["eng"], rt["kbpn"], rt["psp"], self.pc
         kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
         self._invalidate()              # master weights may have been stepped by the optimiser
@@ -368,6 +414,8 @@ class JointModelWithLoss(_JointBase):
         vector [B,kk] instead of KBPN's -- e.g. the reference's own sr_preds from a golden fixture -- so the detector, the losses
         and their backward can be compared with the reference on identical inputs.  ``backward()`` on the returned losses stops at
         the SR image: its gradient (true scale) is left in ``self.last_dsr`` / ``self.last_dkvec``; KBPN parameters get no gradient."""
+        if self.bicubic:
+            raise NotImplementedError("forward_from_sr / kbpn_backward_from are entry points of the KBPN model; MODEL.SR='bicubic' has no SR loss")
         rt = self._runtime()
         self._invalidate()
         x, hr, mask, kgt = self._mount(x), self._mount(sr_targets), self._mount(segment_targets), self._mount(kernel_targets)
@@ -379,6 +427,8 @@ class JointModelWithLoss(_JointBase):
     def kbpn_backward_from(self, iter, x, kernel_targets, dsr, dkvec):
         """Validation entry point: KBPN forward + backward with a GIVEN upstream gradient (dLoss/d sr_preds [B,3,H,W] and
         dLoss/d kernel vector [B,kk], true scale) -- e.g. the reference's own, from a golden fixture.  Returns {state_dict name: grad}."""
+        if self.bicubic:
+            raise NotImplementedError("forward_from_sr / kbpn_backward_from are entry points of the KBPN model; MODEL.SR='bicubic' has no KBPN")
         rt = self._runtime()
         eng, kbpn, pc = rt["eng"], rt["kbpn"], self.pc
         kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
@@ -400,7 +450,7 @@ class JointModelWithLoss(_JointBase):
         eng.join_wgrad()
         return {k: (rt["P"][k].gacc / gs if getattr(rt["P"][k], "gacc_touched", False) else None) for k in names}
 
-    def _detector_and_losses(self, iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=None):
+    def _detector_and_losses(self, iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=None, sr_terms=True):
         rt, pc = self._rt, self.pc
         eng, psp = rt["eng"], rt["psp"]
         B, _, h, w = x.shape
@@ -428,6 +478,12 @@ class JointModelWithLoss(_JointBase):
             L.call("csbsr_segloss_reduce", _ptr(p_), _ptr(mask), _ptr(sdf), B, hw, _ptr(sums), pw[0], pw[1], eng.stream)
             L.call("csbsr_segloss_finish", _ptr(p_), _ptr(mask), _ptr(sdf), B, hw, _ptr(sums), alpha, pw[0], pw[1], lw[0], lw[1], wgt,
                    None, _ptr(seg_loss), None, 0, eng.stream)
+        if not sr_terms:        # MODEL.SR="bicubic": no SR loss, and the graph ends at the detector's input
+            if keep:
+                st = dict(iter=iter, mask=mask, seg32=seg32, aux32=aux32, sdf=sdf, sums_m=sums_m, sums_a=sums_a, alpha=alpha, B=B, h=h, w=w,
+                          psp_saved=psp_saved, detector_only=True)
+                seg_loss = _SegFn.apply(self, st, seg_loss, *[p for p in self.parameters()])
+            return seg_loss, None, seg32, sr32, torch.zeros_like(kgt)
         # KBPNLoss: L1(sr, hr), L1(down(blur(sr)), x), MSE(kernel) * 0
         ksum = kvec.sum(1, keepdim=True)
         vec = (kvec / ksum).contiguous()
@@ -513,7 +569,8 @@ class JointModelWithLoss(_JointBase):
         for k in pnames:                    # fresh fp32 accumulators for this backward
             rt["P"][k].gacc_touched = False
         torch._foreach_zero_(list(rt["flat"].values()))      # the accumulators are views of a handful of flat buckets
-        dsr32 = eng.f32(B, 3, H, W)
+        detector_only = bool(st.get("detector_only"))      # MODEL.SR="bicubic": the input is no function of a parameter
+        dsr32 = None if detector_only else eng.f32(B, 3, H, W)
         # which halves of the backward run follows from which loss vector the caller's scalar loss used (autograd hands None for an
         # unused output): a function of the training phase, identical on every rank, and no device read-back
         seg_active = dseg_loss is not None
@@ -525,8 +582,10 @@ class JointModelWithLoss(_JointBase):
             for p_, sums, wgt, dp in ((st["seg32"], st["sums_m"], self.main_weight, dseg32), (st["aux32"], st["sums_a"], self.aux_weight, daux32)):
                 L.call("csbsr_segloss_finish", _ptr(p_), _ptr(st["mask"]), _ptr(st["sdf"]), B, hw, _ptr(sums), st["alpha"], pw[0], pw[1],
                        lw[0], lw[1], wgt, _ptr(gsc), None, _ptr(dp), 0, eng.stream)
-            dxin = psp.backward(dseg32, daux32)
+            dxin = psp.backward(dseg32, daux32, need_dxin=not detector_only)
             eng.join_wgrad()                    # the detector's weight gradients (side stream) are complete
+            if detector_only:                   # no first-conv input gradient, no csbsr_instnorm_bwd, no last_dsr
+                return self._finish_backward(pnames, gs, ("segmentation_model",), st)
             if self.blur_skip:                  # only blur_skip.* trains: no gradient leaves the segmentation net
                 return self._finish_backward(pnames, gs, ("segmentation_model",), st)
             if self.reducer is not None:        # segmentation gradients are final: exchange them under the KBPN backward
@@ -543,7 +602,7 @@ class JointModelWithLoss(_JointBase):
             del dxin, dseg32, daux32
         else:
             psp.saved = None
-            if self.blur_skip:
+            if self.blur_skip or detector_only:
                 return self._finish_backward(pnames, gs, (), st)
         # ---- SR loss gradients
         dkvec = eng.f32(B, pc.ksize_out ** 2)
@@ -641,6 +700,14 @@ class JointModel(_JointBase):
     def forward(self, x, damy_kernel, sr_targets=None):
         rt = self._runtime()
         eng, kbpn, psp = rt["eng"], rt["kbpn"], rt["psp"]
+        if self.bicubic:        # build_model.py:69-73 + clip_sr: the clip is the up-sampler's own
+            self._invalidate()
+            x, kgt = self._mount(x), self._mount(damy_kernel)
+            sr32 = self._bicubic_up(x, clip=True)
+            xin, _, _ = self._norm_sr(sr32)
+            seg32, _ = psp.forward(xin, {k: None for k in psp.drop_keys}, training=self.training)
+            psp.saved = None
+            return sr32, seg32, torch.zeros_like(kgt)
         kbpn.training_mode = self.training
         self._invalidate()
         x, kgt = self._mount(x), self._mount(damy_kernel)

@@ -389,11 +389,12 @@ class HRNetOCR:
         conv.bwd_weights(dpre, x)
         return conv.bwd_input(dpre)
 
-    def backward(self, dseg32, daux32):
+    def backward(self, dseg32, daux32, need_dxin=True):
+        """``need_dxin=False`` (the input is no function of a parameter: MODEL.SR="bicubic") skips the first conv's input gradient: None."""
         sv = self.saved
         dcat = self._head_bwd(dseg32, daux32)
         self.saved = None
-        return self._backbone_bwd(dcat, sv["ysz"])
+        return self._backbone_bwd(dcat, sv["ysz"], need_dxin)
 
     def _head_bwd(self, dseg32, daux32):
         e, sv, P = self.eng, self.saved, self.P
@@ -439,7 +440,7 @@ class HRNetOCR:
         self.aux0.bwd(da, dx_out=dcat, dx_acc=True)
         return dcat
 
-    def _backbone_bwd(self, dcat, ysz):
+    def _backbone_bwd(self, dcat, ysz, need_dxin=True):
         e = self.eng
         B = dcat.N
         # concat -> branch gradients
@@ -476,4 +477,4 @@ class HRNetOCR:
         for blk in reversed(self.layer1):
             d = blk.bwd(d)
         d = self.stem[1].bwd(d)
-        return self.stem[0].bwd(d)
+        return self.stem[0].bwd(d, need_dx=need_dxin)

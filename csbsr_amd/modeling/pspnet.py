@@ -277,8 +277,9 @@ class PSPNet:
             conv.bwd_weights(dpre, x)
         return conv.bwd_input(dpre)
 
-    def backward(self, dseg32, daux32):
-        """Gradients (scaled) wrt the two probability maps -> returns FM gradient wrt xin [B,H,W,8]."""
+    def backward(self, dseg32, daux32, need_dxin=True):
+        """Gradients (scaled) wrt the two probability maps -> returns FM gradient wrt xin [B,H,W,8]; ``need_dxin=False`` (the input is no
+        function of a parameter: MODEL.SR="bicubic") skips the stem's input gradient and returns None."""
         e, sv = self.eng, self.saved
         drop = sv["drop"]
         xin = sv["xin"]
@@ -355,6 +356,6 @@ class PSPNet:
         L.call("csbsr_maxpool3x3s2_bwd_split", _ptr(a.t), a.ld, a.lo, _ptr(p.t), p.ld, p.lo, _ptr(dy.t), _ptr(da.t), B, a.H, a.W, 64, e.stream)
         draw = self.stem.bn.backward(da, raw, m, iv, act=L.ACT_RELU)
         self.stem.conv.bwd_weights(draw, xin)
-        dxin = self.stem.conv.bwd_input(draw, in_hw=(H, W))
+        dxin = self.stem.conv.bwd_input(draw, in_hw=(H, W)) if need_dxin else None
         self.saved = None
         return dxin

@@ -65,10 +65,21 @@ def _mix(seg, sr, iteration, cfg):
     return calc_pretrain_loss((1 - w) * sr + w * seg, seg, sr, iteration, cfg)
 
 
+def _detector_only(cfg):
+    """MODEL.SR == "bicubic" (trainer.py:414): the loss is the segmentation mean -- no pretraining window, no task weight, no SR loss"""
+    return cfg.MODEL.SR == "bicubic"
+
+
 def calc_loss(segment_loss, sr_loss, iteration, cfg):
     """Per-sample loss vectors -> the scalar that is back-propagated.  A loss vector the scalar does not use gets no gradient, which is how
-    the model's backward knows that a pretraining phase skips one half."""
-    return _mix(segment_loss.mean(), sr_loss.mean(), iteration, cfg)
+    the model's backward knows that a pretraining phase skips one half.  With MODEL.SR == "bicubic" ``sr_loss`` may be None and the scalar
+    is the segmentation mean at every iteration."""
+    return _scalar(segment_loss.mean(), None if sr_loss is None else sr_loss.mean(), iteration, cfg)
+
+
+def _scalar(seg, sr, iteration, cfg):
+    """the rule of ``calc_loss`` on the two batch means (``sr`` may be None with MODEL.SR == "bicubic")"""
+    return seg if _detector_only(cfg) else _mix(seg, sr, iteration, cfg)
 
 
 def set_alpha_phase(cfg, model, iteration):
@@ -192,6 +203,9 @@ class ValidationAccumulator:
         self.rows.append(None)
 
     def add(self, segment_loss, sr_loss, psnr, ssim, kernel_psnr, iou):
+        """``sr_loss`` None (a model without an SR loss: MODEL.SR == "bicubic") adds nothing to the SR sum (trainer.py:160-163)."""
+        if sr_loss is None:
+            sr_loss = torch.zeros_like(torch.as_tensor(segment_loss))
         if self.pg is not None:
             seg, sr = torch.as_tensor(segment_loss).double().reshape(-1), torch.as_tensor(sr_loss).double().reshape(-1)
             self.rows.append(torch.stack([seg.sum(), sr.sum(), seg.new_tensor(float(seg.numel()))]))
@@ -445,8 +459,9 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
         x, hr, mask, k = batch[:4]
         extra = {"segment_sdf": batch[4]} if len(batch) > 4 else {}
         segment_loss, sr_loss = model(iteration, x, sr_targets=hr, segment_targets=mask, kernel_targets=k, **extra)[:2]
-        seg, sr = segment_loss.mean(), sr_loss.mean()
-        loss = _mix(seg, sr, iteration, cfg)
+        # (no SR loss -- MODEL.SR == "bicubic" -- : its window sum stays 0 and the scalar is the segmentation mean, see calc_loss)
+        seg, sr = segment_loss.mean(), (segment_loss.new_zeros(()) if sr_loss is None else sr_loss.mean())
+        loss = _scalar(seg, sr, iteration, cfg)
         loss.backward()
         optimizer.step()
         scheduler.step()

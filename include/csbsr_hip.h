@@ -478,6 +478,12 @@ int csbsr_bilinear32_bwd(const float* dy, float* dx, int32_t planes, int32_t H, 
 /* nn.Upsample(scale_factor, 'bicubic') of the LR input added to the SR residual (kbpn.py:110-114) */
 int csbsr_bicubic_up_add(const float* x, float* out, int32_t planes, int32_t H, int32_t W, int32_t scale,
                          csbsr_stream_t s);
+/* MODEL.SR = "bicubic": transforms.Resize(size * scale, BICUBIC) of the float LR batch (build_model.py:69-73), i.e.
+ * y[planes][H*scale][W*scale] = F.interpolate(x, mode='bicubic', align_corners=False, antialias) -- antialias != 0: A = -0.5, taps cut
+ * to the image and renormalised; antialias == 0: A = -0.75, tap indices clamped.  clip != 0 clamps the result to [0, 1] (clip_sr,
+ * build_model.py:143-146, and trainer.py:172's clipping) in the same pass.  scale: a multiple of 4; y 16-byte aligned. */
+int csbsr_aa_bicubic_up(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t scale,
+                        int32_t antialias, int32_t clip, csbsr_stream_t s);
 /* FactorResize('bicubic') = F.interpolate(bicubic, antialias) by an integer factor (transforms.py:505-531) */
 int csbsr_aa_bicubic_down_fwd(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t f,
                               int32_t antialias, csbsr_stream_t s);
