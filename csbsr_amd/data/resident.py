@@ -129,20 +129,25 @@ def split_resized_crop(augmentation):
 class ResidentDataset:
     """uint8 images (H x W x 3) and masks (H x W or H x W x 1) packed back to back into one contiguous device pool per kind, with an
     int64 byte-offset table and an int32 (H, W) table.  Sizes may differ between samples, not within a pair.  ``subset`` / ``split``
-    return views on the same pools."""
+    return views on the same pools.
 
-    def __init__(self, images, masks, device="cuda:0"):
-        if len(images) != len(masks) or len(images) == 0:
-            raise ValueError(f"{len(images)} images, {len(masks)} masks")
+    ``masks=None`` is the image-only dataset of SR pretraining (the reference's SRPretrainDataSet): there is no mask pool (``mask`` and its
+    aliases are None), ``sample`` returns ``(image, None)``, the gathers return ``(hr, None)`` and a DeviceTrainLoader over it yields
+    ``(x, hr, k)``."""
+
+    def __init__(self, images, masks=None, device="cuda:0"):
+        if (masks is not None and len(images) != len(masks)) or len(images) == 0:
+            raise ValueError(f"{len(images)} images, {'no' if masks is None else len(masks)} masks")
         self.device = torch.device(device)
         self.image = U8Pool(images, 3, "image", self.device)
-        self.mask = U8Pool(masks, 1, "mask", self.device)
-        for i, (a, m) in enumerate(zip(self.image.dims, self.mask.dims)):
+        self.mask = None if masks is None else U8Pool(masks, 1, "mask", self.device)
+        for i, (a, m) in enumerate(zip(self.image.dims, () if self.mask is None else self.mask.dims)):
             if tuple(a) != tuple(m):
                 raise ValueError(f"sample {i}: image {tuple(int(v) for v in a)} and mask {tuple(int(v) for v in m)} differ in size")
         # the pools' tensors and tables under this class's names (plain aliases: ``subset`` copies them with __dict__)
         self.image_pool, self.image_offsets, self.image_offsets_dev = self.image.pool, self.image.offsets, self.image.offsets_dev
-        self.mask_pool, self.mask_offsets, self.mask_offsets_dev = self.mask.pool, self.mask.offsets, self.mask.offsets_dev
+        self.mask_pool, self.mask_offsets, self.mask_offsets_dev = (None, None, None) if self.mask is None else \
+            (self.mask.pool, self.mask.offsets, self.mask.offsets_dev)
         self.dims, self.dims_dev = self.image.dims, self.image.dims_dev
         self.indices = np.arange(len(images), dtype=np.int64)                             # pool indices this view holds
 
@@ -166,12 +171,23 @@ class ResidentDataset:
         ds.names = names
         return ds
 
+    @classmethod
+    def from_image_dir(cls, image_dir, pattern="*.png", device="cuda:0"):
+        """The image-only dataset of SR pretraining: every ``pattern`` file under ``image_dir`` (the reference's SRPretrainDataSet globs
+        ``*.png``), decoded once with PIL as ``from_dirs`` decodes its images."""
+        names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(image_dir, pattern)))
+        if not names:
+            raise FileNotFoundError(f"no {pattern} under {image_dir}")
+        ds = cls([decode_u8(os.path.join(image_dir, n), 3, "8-bit RGB (H x W x 3)", what="image ") for n in names], None, device=device)
+        ds.names = names
+        return ds
+
     def __len__(self):
         return len(self.indices)
 
     @property
     def nbytes(self):
-        return int(self.image_pool.numel() + self.mask_pool.numel())
+        return int(self.image_pool.numel() + (0 if self.mask is None else self.mask_pool.numel()))
 
     def subset(self, indices):
         """A view on the same pools holding ``indices`` (positions in this view)."""
@@ -191,9 +207,9 @@ class ResidentDataset:
         return self.subset(perm[:k]), self.subset(perm[k:])
 
     def sample(self, i):
-        """(image H x W x 3, mask H x W x 1) uint8 numpy copies of sample ``i`` of this view."""
+        """(image H x W x 3, mask H x W x 1) uint8 numpy copies of sample ``i`` of this view; the mask is None without a mask pool."""
         p = int(self.indices[i])
-        return self.image.sample(p), self.mask.sample(p)
+        return self.image.sample(p), None if self.mask is None else self.mask.sample(p)
 
     def check_selection(self, sel, h, w):
         """Raise unless every row (index, y0, x0, mirror, vflip) of ``sel`` names a pooled image and an h x w window inside it."""
@@ -206,16 +222,17 @@ class ResidentDataset:
     def gather_resized(self, sel_dev, B, h, w, antialias=True):
         """(hr [B,3,h,w], mask [B,1,h,w]) fp32: the hs x ws window of each row of the int32 [B][7] device table ``sel_dev`` (validated by
         the caller, check_windows) resampled to h x w like F.interpolate(mode="bilinear", antialias=antialias), / 255.  The mask goes
-        through the same resample (transforms.py:619-620) and comes out soft."""
+        through the same resample (transforms.py:619-620) and comes out soft; None, and no launch, without a mask pool."""
         if self.device.type != "cuda":
             raise L.CsbsrHipError("ResidentDataset.gather_resized needs the pool on a GPU: csbsr_amd has no fallback path")
-        return self.image.gather_resized(sel_dev, B, h, w, antialias), self.mask.gather_resized(sel_dev, B, h, w, antialias)
+        return self.image.gather_resized(sel_dev, B, h, w, antialias), None if self.mask is None else self.mask.gather_resized(sel_dev, B, h, w, antialias)
 
     def gather(self, sel_dev, B, h, w):
-        """(hr [B,3,h,w], mask [B,1,h,w]) fp32 = pool bytes / 255 for the int32 [B][5] device table ``sel_dev`` (validated by the caller)."""
+        """(hr [B,3,h,w], mask [B,1,h,w]) fp32 = pool bytes / 255 for the int32 [B][5] device table ``sel_dev`` (validated by the caller);
+        the mask is None, and no launch, without a mask pool."""
         if self.device.type != "cuda":
             raise L.CsbsrHipError("ResidentDataset.gather needs the pool on a GPU: csbsr_amd has no fallback path")
-        return self.image.gather(sel_dev, B, h, w), self.mask.gather(sel_dev, B, h, w)
+        return self.image.gather(sel_dev, B, h, w), None if self.mask is None else self.mask.gather(sel_dev, B, h, w)
 
 
 _ROW = 32          # staged bytes per sample: int32 [5] selection row, then fp32 [3] blur parameters (40 with the [7] rows of resized_crop)
@@ -225,7 +242,11 @@ _SLOTS = 4         # staging ring: a slot is rewritten four batches after its up
 
 class DeviceTrainLoader:
     """Iterating yields ``(x_lr, hr, mask, kernels, sdf)`` on the device, the argument order of
-    ``JointModelWithLoss.forward(iter, x, sr_targets, segment_targets, kernel_targets, segment_sdf=)``.
+    ``JointModelWithLoss.forward(iter, x, sr_targets, segment_targets, kernel_targets, segment_sdf=)``.  Over an image-only dataset
+    (``ResidentDataset(images)``) it yields ``(x_lr, hr, kernels)``, the reference's ONLY_IMAGES tuple and the argument order of
+    ``SRModelWithLoss.forward(iter, x, sr_targets, kernel_targets)``: no mask is gathered and no SDF computed, every decision (indices,
+    windows, flips, blur parameters) is the one a loader over the same images with masks takes for the same seed, and ``x``, ``hr`` and
+    ``k`` are the same bytes.  ``shard=`` with world > 1 is refused there: data-parallel pretraining is not built.
 
     Sampling (train.py:60-62): one permutation of the shard's samples per epoch, without replacement (RandomSampler); batches of
     ``batch_size``, the last of an epoch short unless ``drop_last`` (BatchSampler); epochs repeat until ``num_iterations`` batches have
@@ -293,6 +314,9 @@ class DeviceTrainLoader:
         if shard_mode not in ("sample", "batch"):
             raise ValueError(f"shard_mode {shard_mode!r}: 'sample' or 'batch'")
         self.shard_mode, self.rank, self.world = shard_mode, rank, world
+        self.image_only = getattr(dataset, "mask", None) is None
+        if self.image_only and world > 1:
+            raise NotImplementedError("an image-only dataset feeds SR pretraining, which is single-GPU: shard=(rank, world > 1) is not built")
         if shard_mode == "batch":
             if self.shuffle and world > 1 and not self.drop_last:
                 raise ValueError("shard_mode='batch' with shuffle=True and world > 1 needs drop_last=True: a short global batch at the end "
@@ -417,7 +441,8 @@ class DeviceTrainLoader:
         return dev[:B * 4 * cols].view(torch.int32).view(B, cols), dev[B * 4 * cols:].view(torch.float32).view(B, 3)
 
     def batch(self, sel, blur_params=None):
-        """Decisions -> (x_lr [B,3,h/s,w/s], hr [B,3,h,w], mask [B,1,h,w], kernels [B,1,K,K], sdf [B,1,h,w]).  ``sel`` ([B,5], or [B,7] with
+        """Decisions -> (x_lr [B,3,h/s,w/s], hr [B,3,h,w], mask [B,1,h,w], kernels [B,1,K,K], sdf [B,1,h,w]), or (x_lr, hr, kernels) over an
+        image-only dataset.  ``sel`` ([B,5], or [B,7] with
         ``resized_crop``) is validated on the host first.  No wait on the batch's own work: the host may only block on the upload issued four batches earlier (_upload)."""
         sel = torch.as_tensor(sel)
         if self.resized_crop is not None:
@@ -441,12 +466,13 @@ class DeviceTrainLoader:
             else:
                 hr, mask = self.dataset.gather(sel_dev, B, self.h, self.w)
             if self.blur:
-                return self.deg(hr, mask, params=params_dev)
+                out = self.deg(hr, mask, params=params_dev)
+                return (out[0], out[1], out[3]) if self.image_only else out
             k = torch.zeros(B, 1, self.K, self.K, dtype=torch.float32, device=self.device)
             k[:, :, self.K // 2, self.K // 2] = 1.0
             x = torch.empty(B, 3, self.h // self.scale, self.w // self.scale, dtype=torch.float32, device=self.device)
             L.call("csbsr_aa_bicubic_down_fwd", _ptr(hr), _ptr(x), B * 3, self.h, self.w, self.scale, int(self.antialias), self.deg._stream)
-            return x, hr, mask, k, self.deg.sdf(mask)
+            return (x, hr, k) if self.image_only else (x, hr, mask, k, self.deg.sdf(mask))
 
     def __len__(self):
         if self.num_iterations is not None:

@@ -4,6 +4,8 @@
         .forward(iter, x, sr_targets=None, segment_targets=None, kernel_targets=None)
             -> (segment_loss[B], sr_loss[B], segment_preds, sr_preds, kernel_preds[B,1,K,K])
     JointModel(cfg).forward(x, damy_kernel, sr_targets=None) -> (sr_preds, segment_preds, kernel_preds)
+    SRModelWithLoss(cfg, sr_transforms, num_train_ds, resume_iter)
+        .forward(iter, x, sr_targets=None, kernel_targets=None) -> (sr_loss[B], sr_preds, kernel_preds[B,1,K,K])
 
 (/root/reference/model/modeling/build_model.py:323-416, 441-500).  Same constructor / forward signatures,
 same state_dict keys, same attributes the trainer touches (``sr_model``, ``segmentation_model``,
@@ -16,6 +18,7 @@ backward pass; PyTorch only owns memory, streams and the optimizer.
 """
 import ctypes as C
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -23,6 +26,7 @@ import torch.nn as nn
 from .. import _lib as L
 from ..config import path_config
 from ..engine import Engine, FM, grad_acc, _ptr
+from ..utils.misc import fix_model_state_dict
 from .kbpn import KBPN
 from .pspnet import PSPNet
 from .hrnet_ocr import HRNetOCR
@@ -96,13 +100,45 @@ def _init_reference_style(name, t, gen):
             t.zero_()
 
 
+def pretrained_sr_path(cfg, root="weights"):
+    """``<root>/pretrain/KBPN_pretrain_x{SCALE}_stage{S}[_bicubic{K}].pth`` (build_model.py:104-107): the file the SR-only regime leaves
+    and every model with ``MODEL.SR_SCRATCH = False`` starts from; ``_bicubic{K}`` when BLUR.KERNEL_SIZE != BLUR.KERNEL_SIZE_OUTPUT."""
+    name = f"KBPN_pretrain_x{cfg.MODEL.SCALE_FACTOR}_stage{cfg.MODEL.NUM_STAGES}"
+    if cfg.BLUR.KERNEL_SIZE != cfg.BLUR.KERNEL_SIZE_OUTPUT:
+        name += f"_bicubic{cfg.BLUR.KERNEL_SIZE}"
+    return os.path.join(root, "pretrain", name + ".pth")
+
+
+def load_pretrained_sr(model, cfg, root="weights"):
+    """build_model.py:108-109: the file's keys lose ``len("sr_model.")`` leading characters (fix_model_state_dict), the load is
+    non-strict (tensors the file does not name keep their init) and any key KBPN does not have is an error.  Returns the path."""
+    path = pretrained_sr_path(cfg, root)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"MODEL.SR_SCRATCH=False needs the pretrained KBPN weights {path}")
+    sd = fix_model_state_dict(torch.load(path, map_location="cpu"), addition_word="sr_model.")
+    own = dict(model.sr_model.named_local())
+    unexpected = [k for k in sd if k not in own]
+    if unexpected:
+        raise RuntimeError(f"unexpected_keys are exist in {path}.\n {unexpected[:8]}")
+    with torch.no_grad():
+        for k, v in sd.items():
+            own[k].copy_(v)
+    return path
+
+
 class _JointBase(nn.Module):
-    def __init__(self, cfg, antialias=True, device="cuda:0", seed=None):
+    def __init__(self, cfg, antialias=True, device="cuda:0", seed=None, pretrained_root="weights", sr_only=False):
         super().__init__()
+        # ``sr_only`` (SRModelWithLoss): KBPN and its loss alone -- no detector is constructed, moved to the device or given a gradient bucket
+        self.sr_only = bool(sr_only)
         # MODEL.SR="bicubic" (build_model.py:69-73, 90-91): the paper's lower-bound row, the detector on the bicubically up-scaled LR image.
         # PSPNet_BlurSkip is not built with it: its SFT layers are fed KBPN's kernel estimate, which this model does not have
-        self.bicubic = cfg.MODEL.SR == "bicubic"
-        if cfg.MODEL.SR not in ("KBPN", "bicubic") or cfg.MODEL.DETECTOR_TYPE not in ("PSPNet", "PSPNet_BlurSkip", "HRNet_OCR") or \
+        self.bicubic = cfg.MODEL.SR == "bicubic" and not self.sr_only
+        if self.sr_only:
+            if cfg.MODEL.SR != "KBPN" or cfg.MODEL.SCALE_FACTOR == 1 or cfg.MODEL.SR_SEG_INV:
+                raise NotImplementedError(f"csbsr_amd pretrains MODEL.SR='KBPN' on 3-channel images at SCALE_FACTOR > 1; got SR={cfg.MODEL.SR} "
+                                          f"SCALE_FACTOR={cfg.MODEL.SCALE_FACTOR} SR_SEG_INV={cfg.MODEL.SR_SEG_INV}")
+        elif cfg.MODEL.SR not in ("KBPN", "bicubic") or cfg.MODEL.DETECTOR_TYPE not in ("PSPNet", "PSPNet_BlurSkip", "HRNet_OCR") or \
                 (self.bicubic and cfg.MODEL.DETECTOR_TYPE == "PSPNet_BlurSkip"):
             raise NotImplementedError(f"csbsr_amd builds KBPN + PSPNet / PSPNet_BlurSkip / HRNet_OCR and bicubic + PSPNet / HRNet_OCR; got "
                                       f"SR={cfg.MODEL.SR} DETECTOR_TYPE={cfg.MODEL.DETECTOR_TYPE}")
@@ -110,28 +146,31 @@ class _JointBase(nn.Module):
             raise NotImplementedError(f"MODEL.SR='bicubic' with SCALE_FACTOR={cfg.MODEL.SCALE_FACTOR}: a multiple of 4")
         if cfg.MODEL.SUM_LR_ERROR_POS not in ("HR", "LR"):      # kbpn.py:174-187: the reference's forward handles exactly these two
             raise NotImplementedError(f"MODEL.SUM_LR_ERROR_POS={cfg.MODEL.SUM_LR_ERROR_POS!r}: 'HR' or 'LR'")
-        if cfg.MODEL.NUM_CLASSES != 1:      # build_model.py:209: every kernel of this path assumes the 1-class crack map
-            raise NotImplementedError(f"MODEL.NUM_CLASSES={cfg.MODEL.NUM_CLASSES}: only the 1-class detectors are built")
-        if cfg.MODEL.SR_SEG_INV or not cfg.MODEL.JOINT_LEARNING:
-            raise NotImplementedError("only MODEL.JOINT_LEARNING=True with SR_SEG_INV=False (SR feeds the detector, one joint loss) is built")
+        if not self.sr_only:
+            if cfg.MODEL.NUM_CLASSES != 1:      # build_model.py:209: every kernel of this path assumes the 1-class crack map
+                raise NotImplementedError(f"MODEL.NUM_CLASSES={cfg.MODEL.NUM_CLASSES}: only the 1-class detectors are built")
+            if cfg.MODEL.SR_SEG_INV or not cfg.MODEL.JOINT_LEARNING:
+                raise NotImplementedError("only MODEL.JOINT_LEARNING=True with SR_SEG_INV=False (SR feeds the detector, one joint loss) is built")
         self.cfg = cfg
         self.pc = path_config(cfg, antialias)
         self.scale_factor = cfg.MODEL.SCALE_FACTOR
         self.norm_method = cfg.SOLVER.NORM_SR_OUTPUT
-        self.seg_model_name = cfg.MODEL.DETECTOR_TYPE
+        self.seg_model_name = None if self.sr_only else cfg.MODEL.DETECTOR_TYPE
         self.blur_skip = self.seg_model_name == "PSPNet_BlurSkip"
         self._device = torch.device(device)
-        shapes = joint_state_shapes(self.pc.scale, self.pc.num_stages, self.pc.ksize, self.pc.ksize_out, self.seg_model_name,
+        shapes = joint_state_shapes(self.pc.scale, self.pc.num_stages, self.pc.ksize, self.pc.ksize_out, self.seg_model_name or "PSPNet",
                                     pixel_shuffle=self.pc.pixel_shuffle, kernel_sft=self.pc.kernel_sft, lr_error=self.pc.lr_error,
                                     zero_pad_kernel=self.pc.zero_pad_kernel)
         # registration order = reference state_dict order: segmentation_model.* then sr_model.*
-        self.segmentation_model = _ParamGroup(shapes, "segmentation_model")
+        self.segmentation_model = None if self.sr_only else _ParamGroup(shapes, "segmentation_model")
         # (bicubic: the reference's ``sr_model`` is this string and its state_dict / parameters() hold the detector alone)
         self.sr_model = "bicubic" if self.bicubic else _ParamGroup(shapes, "sr_model")
         gen = torch.Generator().manual_seed(cfg.SEED if seed is None else seed)
         for full, t in self._named_full():
             if t.is_floating_point() and not full.endswith(("running_mean", "running_var")):
                 _init_reference_style(full, t.data, gen)
+        if not self.bicubic and not cfg.MODEL.SR_SCRATCH:      # build_model.py:101-110; the detector's tensors keep the seeded init above
+            self.pretrained_sr_path = load_pretrained_sr(self, cfg, pretrained_root)
         if self.blur_skip:        # build_model.py:352-368: everything but blur_skip.* is fixed
             for full, t in self._named_full():
                 if isinstance(t, nn.Parameter):
@@ -183,7 +222,7 @@ class _JointBase(nn.Module):
 
     # ---- naming: state_dict keys are the reference's dotted names
     def _named_full(self):
-        for grp in ("segmentation_model",) if self.bicubic else ("segmentation_model", "sr_model"):
+        for grp in ("sr_model",) if self.sr_only else ("segmentation_model",) if self.bicubic else ("segmentation_model", "sr_model"):
             for local, t in getattr(self, grp).named_local():
                 yield f"{grp}.{local}", t
 
@@ -214,9 +253,11 @@ class _JointBase(nn.Module):
             self.to(self._device)
             eng = Engine(self._device)
             P = {k: (v.data if isinstance(v, nn.Parameter) else v) for k, v in self._named_full()}
-            self._rt = {"eng": eng, "P": P, "kbpn": None if self.bicubic else KBPN(eng, P, self.pc), "psp": HRNetOCR(eng, P) if self.seg_model_name == "HRNet_OCR"
-                        else PSPNet(eng, P, blur_dim=self.pc.ksize_out ** 2 if self.blur_skip else None)}
+            self._rt = {"eng": eng, "P": P, "kbpn": None if self.bicubic else KBPN(eng, P, self.pc), "psp": None if self.sr_only else HRNetOCR(eng, P)
+                        if self.seg_model_name == "HRNet_OCR" else PSPNet(eng, P, blur_dim=self.pc.ksize_out ** 2 if self.blur_skip else None)}
             self._make_grad_buckets()
+        if self._rt["psp"] is None:        # SR-only: no detector, so no detector precision plan to apply
+            return self._rt
         if self.detector_precision not in ("fp16", "split"):
             raise ValueError(f"detector_precision must be 'fp16' or 'split', got {self.detector_precision!r}")
         split = self.detector_precision == "split"
@@ -263,7 +304,8 @@ class _JointBase(nn.Module):
         rt = self._rt
         if rt["kbpn"] is not None:
             rt["kbpn"].invalidate()
-        rt["psp"].invalidate()
+        if rt["psp"] is not None:
+            rt["psp"].invalidate()
         rt["eng"].new_step()            # (master weights may have been stepped: every PReLU slope probe may issue one new asynchronous read)
 
     # ---- shared forward pieces
@@ -338,51 +380,43 @@ class _SegFn(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
-class JointModelWithLoss(_JointBase):
-    def __init__(self, cfg, num_train_ds, resume_iter, sr_transforms=None, antialias=True, device="cuda:0", seed=None):
-        super().__init__(cfg, antialias, device, seed)
-        # bicubic: calc_sr_loss returns None before it looks at the loss function (build_model.py:163-166), so the keys that only shape
-        # KBPN or the SR loss have no effect, as in the reference (the list: DESIGN.md section 1.5); _JointBase's refusals of values no model
-        # of this build takes (SUM_LR_ERROR_POS, NUM_CLASSES, SR_SEG_INV, JOINT_LEARNING) hold for this model too
-        if cfg.SOLVER.SEG_LOSS_FUNC != "BoundaryCombo" or (cfg.SOLVER.SR_LOSS_FUNC != "KBPN" and not self.bicubic):
-            raise NotImplementedError("csbsr_amd builds SEG_LOSS_FUNC=BoundaryCombo with SR_LOSS_FUNC=KBPN")
-        if cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SS_AMP != 0 or cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0 or cfg.SOLVER.INTERM_SSLOSSWEGHT4SR:
-            raise NotImplementedError("oriented loss weights other than SEG_FAIL_ORIENTED_WEIGHT4SR are not built")
-        seg_rsm = resume_iter - (cfg.SOLVER.SR_PRETRAIN_ITER[1] - 1) if resume_iter > (cfg.SOLVER.SR_PRETRAIN_ITER[1] - 1) else 0
-        per_epoch = num_train_ds // cfg.SOLVER.BATCH_SIZE + 1
-        self.ss_loss_fn = BoundaryComboState(per_epoch, seg_rsm, decrease_ratio=cfg.SOLVER.BOUNDARY_DEC_RATIO)
-        self.sr_loss_fn = "KBPNLoss"
-        self.aux_weight, self.main_weight = cfg.SOLVER.SEG_AUX_LOSS_WEIGHT, cfg.SOLVER.SEG_MAIN_LOSS_WEIGHT
-        self.iter_cnt = True
+class _SRFn(torch.autograd.Function):
+    """sr_loss[B] = f(KBPN parameters) of SRModelWithLoss; backward = the SR half of the HIP backward pass."""
+
+    @staticmethod
+    def forward(ctx, model, st, sr_loss, *params):
+        ctx.model, ctx.st = model, st
+        ctx.set_materialize_grads(False)
+        return sr_loss.clone()
+
+    @staticmethod
+    def backward(ctx, dsr):
+        st, ctx.st = ctx.st, None
+        if st is None:
+            raise RuntimeError("csbsr_amd: backward called twice on the same forward (activations are freed by the first backward)")
+        grads = ctx.model._hip_backward(st, dsr)
+        return (None, None, None) + tuple(grads)
+
+
+class _TrainBase(_JointBase):
+    """What JointModelWithLoss and SRModelWithLoss share: the KBPN forward in micro-batches with its residency budget, KBPNLoss, the SR
+    gradient seed, the KBPN backward schedule and the end of a backward (exchange, overflow skip, un-scaling)."""
+
+    def _init_loss_scale(self):
         self.grad_scale = None          # None: chosen per call as 2^round(log2(B*H*W)) (see _hip_backward)
         self.scale_backoff = 0          # log2 reduction of the automatic scale after overflowed steps
         self.overflow_steps = 0
         self.last_step_overflowed = False
-        self.last_dsr = self.last_dkvec = None      # set by the backward of forward_from_sr (validation)
         self.reducer = None             # csbsr_amd.parallel.GradBucketReducer when data-parallel
 
-    # ------------------------------------------------------------------ forward
-    def forward(self, iter, x, sr_targets=None, segment_targets=None, kernel_targets=None, segment_sdf=None):
-        """``segment_sdf`` (optional, not in the reference's signature): the signed distance map of ``segment_targets`` already on the
-        device -- csbsr_amd.data.degrade.DeviceDegradation computes it with the batch -- so the loss does not recompute it."""
-        rt = self._runtime()
-        if self.bicubic:
-            # forward_sr's bicubic branch: sr_preds is the UNCLIPPED up-scaled input, kernel_preds zeros of the target's shape, sr_loss None;
-            # the detector and its loss are the kernels of the joint model's detector half on the same bytes
-            self._invalidate()
-            x, mask, kgt = self._mount(x), self._mount(segment_targets), self._mount(kernel_targets)
-            self._n_res = 0
-            return self._detector_and_losses(iter, x, None, mask, kgt, self._bicubic_up(x, clip=False), None, None, x.shape[0],
-                                             sdf=self._mount(segment_sdf), sr_terms=False)
-        eng, kbpn, psp, pc = rt["eng"], rt["kbpn"], rt["psp"], self.pc
-        kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
-        self._invalidate()              # master weights may have been stepped by the optimiser
-        x, hr, mask, kgt = self._mount(x), self._mount(sr_targets), self._mount(segment_targets), self._mount(kernel_targets)
+    def _kbpn_forward(self, iter, x, kgt):
+        """KBPN over the mounted batch in micro-batches -> (sr32 [B,3,H,W], kvec [B,kk], saves, micro-batch): the first ``n_res``
+        micro-batches keep their activations for the backward (``saves[i]``), the others are recomputed there."""
+        eng, kbpn, pc = self._rt["eng"], self._rt["kbpn"], self.pc
         B, _, h, w = x.shape
         H, W = h * pc.scale, w * pc.scale
         mb = max(1, min(self.micro_batch, B))
-        training = self.training
-        keep = training and torch.is_grad_enabled()
+        keep = self.training and torch.is_grad_enabled()
         # (the rank agreement inside _auto_resident is a collective: only a forward that will be followed by a backward takes part in it, so
         # a rank-0-only validation pass, an evaluator sharing the model or a no_grad call can never leave the other ranks waiting)
         n_res, lean = (self.max_resident, bool(self.lean_saves)) if self.max_resident is not None else self._auto_resident(B, mb, H, W, agree=keep)
@@ -407,6 +441,207 @@ class JointModelWithLoss(_JointBase):
             kbpn.saved = None
             sr32[b0:b0 + mb] = s_
             kvec[b0:b0 + mb] = k_
+        return sr32, kvec, saves, mb
+
+    def _sr_loss_terms(self, iter, x, hr, kgt, sr32, kvec, seg32, mask):
+        """KBPNLoss (sr_loss_functions.py:35-66), forward sums only -> (sr_loss [B], kernel_preds [B,1,K,K], what _sr_loss_seed needs).
+        ``seg32`` / ``mask`` feed the oriented weight map alone; the SR-only model has neither and refuses the keys that would ask for it."""
+        eng, pc = self._rt["eng"], self.pc
+        B, _, h, w = x.shape
+        H, W = h * pc.scale, w * pc.scale
+        hw = H * W
+        # KBPNLoss: L1(sr, hr), L1(down(blur(sr)), x), MSE(kernel) * 0
+        ksum = kvec.sum(1, keepdim=True)
+        vec = (kvec / ksum).contiguous()
+        K = pc.ksize_out
+        wmap = None
+        if iter > pc.oriented_w_iter and pc.oriented_w_iter != -1 and pc.sfo_sr_amp != 0:
+            wmap = torch.exp(pc.sfo_sr_amp * (seg32 - mask).abs()).contiguous()      # oriented_weight.py:73-83 (detached)
+        wmap_lr = None
+        if wmap is not None:
+            wmap_lr = eng.f32(B, 1, h, w, zero=False)
+            L.call("csbsr_bilinear32_fwd", _ptr(wmap), _ptr(wmap_lr), B, H, W, h, w, 0, eng.stream)
+        blurred = eng.f32(B, 3, H, W, zero=False)
+        L.call("csbsr_blur_fwd", _ptr(sr32), _ptr(vec), B, 3, H, W, K, 1, None, _ptr(blurred), None, 0, eng.stream)
+        lr_pred = eng.f32(B, 3, h, w, zero=False)
+        L.call("csbsr_aa_bicubic_down_fwd", _ptr(blurred), _ptr(lr_pred), B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
+        s_hr, s_lr = eng.f32(B), eng.f32(B)
+        L.call("csbsr_l1_fwd_bwd", _ptr(sr32), _ptr(hr), _ptr(wmap), B, 3, hw, _ptr(s_hr), 0.0, None, None, 0, eng.stream)
+        L.call("csbsr_l1_fwd_bwd", _ptr(lr_pred), _ptr(x), _ptr(wmap_lr), B, 3, h * w, _ptr(s_lr), 0.0, None, None, 0, eng.stream)
+        kpred = vec.reshape(B, 1, K, K)
+        k_l = ((kpred - kgt) ** 2).mean((1, 2, 3))
+        # SOLVER.ONLY_KERNEL_LOSS_FOR_PRETRAIN (sr_loss_functions.py:50-51): during the kernel-module pretraining phase the SR loss IS the
+        # kernel MSE (the reference returns the unreduced [B,1,K,K] map there and calc_loss takes its mean: the per-sample mean has the same mean)
+        sr_w = (0.0, 0.0, 1.0) if (pc.only_kernel_loss and pc.kernel_pretrain[0] <= iter < pc.kernel_pretrain[1]) else pc.sr_w
+        sr_loss = sr_w[0] * s_hr / (3 * hw) + sr_w[1] * s_lr / (3 * h * w) + sr_w[2] * k_l
+        del blurred
+        return sr_loss, kpred, dict(ksum=ksum, vec=vec, lr_pred=lr_pred, wmap=wmap, wmap_lr=wmap_lr, sr_w=sr_w)
+
+    def _auto_resident(self, B, mb, H, W, agree=True):
+        """micro-batches whose KBPN activations fit next to the detector's working set -- the SR-only model has none, so its budget has
+        no detector term -- (measured at HR 1792^2: 26.5 GB per image of KBPN activations, 6.3 / 9.5 GB per image for PSPNet / HRNet-OCR incl. their backward workspaces -- the split-precision
+        detector holds two planes per activation) with 18 GB to spare.  The budget is what is FREE now (driver-reported free memory
+        plus what torch's caching allocator holds but does not use), so another tenant of the GPU or a second model in the process
+        lowers the residency instead of running the step out of memory; the rest is recomputed in the backward."""
+        r = (H * W) / float(1792 * 1792)
+        free, _ = torch.cuda.mem_get_info(self._device)
+        free += torch.cuda.memory_reserved(self._device) - torch.cuda.memory_allocated(self._device)
+        det = (9.5e9 if self.seg_model_name == "HRNet_OCR" else 6.3e9) * r * B
+        if self.detector_precision == "split":
+            det += 4.9e9 * r * B
+        if self.sr_only:        # no detector: its working set is KBPN's to keep
+            det = 0.0
+        n_mb = (B + mb - 1) // mb
+
+        def fit(per_img):
+            imgs = int((free - 18e9 - det) // (per_img * r)) if r > 0 else B
+            return max(0, min(n_mb, imgs // mb))
+        full, lean = fit(26.5e9), fit(21.2e9)      # lean saves: the kernel predictors' fe_SR chains are rebuilt in the backward (KBPN.forward)
+        if agree and self.reducer is not None and self.reducer.active:
+            # data-parallel: the ranks must take the SAME schedule (at ~240 of 288 GB the collective library's buffers can tip one rank into
+            # recomputing a KBPN forward, and every other rank would wait for it at the all-reduce): the minimum over the ranks, agreed
+            # in one tiny collective per problem shape.  EVERY rank must present each training shape (B, micro-batch, H, W) -- the
+            # data-parallel contract anyway: equal shards, train.py:105-112 of the reference -- and only training forwards with autograd
+            # on take part (``agree``); eval / no_grad forwards keep nothing resident and use the local figures.  The agreement is kept
+            # for the life of the model: renewing it when ONE rank's free memory drops later would be a collective only that rank enters
+            key = (B, mb, H, W, self.detector_precision)
+            agreed = self.__dict__.setdefault("_sched_agreed", {})
+            if key not in agreed:
+                agreed[key] = self.reducer.agree_min([full, lean])
+            full, lean = agreed[key]
+        if self.lean_saves is not None:
+            return (lean, True) if self.lean_saves else (full, False)
+        return (lean, True) if lean > full else (full, False)
+
+    def _sr_loss_seed(self, st, dsr_loss, gs, dsr32):
+        """Seeds of the KBPN backward from the SR loss: adds dLoss/d sr_preds (x ``gs``) into ``dsr32`` and returns dLoss/d kernel vector
+        [B,kk] (zeros when the caller's scalar did not use the SR loss)."""
+        eng, pc = self._rt["eng"], self.pc
+        B, h, w = st["B"], st["h"], st["w"]
+        H, W = h * pc.scale, w * pc.scale
+        hw = H * W
+        dkvec = eng.f32(B, pc.ksize_out ** 2)
+        if dsr_loss is not None:
+            g = (dsr_loss.to(torch.float32) * gs)
+            K = pc.ksize_out
+            sr_w = st["sr_w"]
+            g_hr = (g * sr_w[0] / (3 * hw)).contiguous()
+            g_lr = (g * sr_w[1] / (3 * h * w)).contiguous()
+            L.call("csbsr_l1_fwd_bwd", _ptr(st["sr32"]), _ptr(st["hr"]), _ptr(st["wmap"]), B, 3, hw, None, 1.0, _ptr(g_hr), _ptr(dsr32), 1,
+                   eng.stream)
+            dlr = eng.f32(B, 3, h, w, zero=False)
+            L.call("csbsr_l1_fwd_bwd", _ptr(st["lr_pred"]), _ptr(st["x"]), _ptr(st["wmap_lr"]), B, 3, h * w, None, 1.0, _ptr(g_lr), _ptr(dlr), 0,
+                   eng.stream)
+            dbl = eng.f32(B, 3, H, W, zero=False)
+            L.call("csbsr_aa_bicubic_down_bwd", _ptr(dlr), _ptr(dbl), 0, B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
+            L.call("csbsr_blur_bwd_input", _ptr(dbl), _ptr(st["vec"]), _ptr(dsr32), 1, B, 3, H, W, K, 1, eng.stream)
+            dvec = eng.f32(B, K * K)
+            L.call("csbsr_blur_bwd_kernel", _ptr(dbl), _ptr(st["sr32"]), _ptr(dvec), B, 3, H, W, K, 1, eng.stream)
+            if sr_w[2] != 0:
+                dvec += (g * sr_w[2] / (K * K)).reshape(B, 1) * 2 * (st["vec"] - st["kgt"].reshape(B, -1))
+            dkvec = (dvec - (dvec * st["vec"]).sum(1, keepdim=True)) / st["ksum"]
+            del dbl, dlr
+        return dkvec
+
+    def _kbpn_backward_schedule(self, st, dsr32, dkvec):
+        """KBPN backward per micro-batch with the upstream gradients ``dsr32`` / ``dkvec`` (x loss scale); returns the buckets whose
+        exchange was launched under it (data-parallel)."""
+        rt = self._rt
+        kbpn = rt["kbpn"]
+        B, mb, saves = st["B"], st["mb"], st["saves"]
+        order = list(enumerate(range(0, B, mb)))
+        # resident micro-batches last-in first-out (frees HBM before the recomputed ones run), then the rest with their forward
+        # recomputed here (KBPN has no batch-coupled op: exact)
+        sched = [(i, b0, False) for i, b0 in reversed(order) if saves[i] is not None] + [(i, b0, True) for i, b0 in order if i >= st["n_res"]]
+        launched = set()
+
+        def stage_done(s):      # last micro-batch only: stage s's parameter gradients are final -> exchange them under the rest
+            if self.reducer is not None:
+                self.reducer.launch_flat(rt["flat"].get(f"kbpn.{s}"))
+                launched.add(f"kbpn.{s}")
+        for j, (i, b0, recompute) in enumerate(sched):
+            if recompute:
+                kbpn.forward(st["x"][b0:b0 + mb], st["iter"], st["kgt"][b0:b0 + mb], save=True,
+                             pad_replay=st["pad_takes"][i] if kbpn.zero_pad else None)
+            else:
+                kbpn.saved, saves[i] = saves[i], None
+            kbpn.backward(dsr32[b0:b0 + mb].contiguous(), dkvec[b0:b0 + mb].contiguous(),
+                          stage_done=stage_done if j == len(sched) - 1 else None)
+        return launched
+
+    def _finish_backward(self, pnames, gs, reduce_groups, st):
+        rt = self._rt
+        rt["eng"].join_wgrad()
+        if self.reducer is not None:
+            # whatever this phase's backward wrote and has not been launched yet (every rank takes the same branch: the set of
+            # buckets depends on the training phase only)
+            for b, flat in rt["flat"].items():
+                grp = "segmentation_model" if b == "seg" else "sr_model"
+                if grp in reduce_groups and not (b == "seg" and st.get("seg_launched")) and b not in st.get("kbpn_launched", ()):
+                    self.reducer.launch_flat(flat)
+            self.reducer.finish()
+        inv = 1.0 / gs
+        # overflow check on the (already all-reduced, so rank-consistent) accumulators: one scalar read back per step
+        finite = bool(torch.isfinite(torch.stack(torch._foreach_norm(list(rt["flat"].values()))).sum()))
+        if not finite:
+            self.overflow_steps += 1
+            if self.grad_scale is None:
+                self.scale_backoff += 4
+            import warnings
+            warnings.warn(f"csbsr_amd: fp16 gradient overflow at loss scale {gs:g}; this step is skipped (every gradient is None)"
+                          + ("" if self.grad_scale is not None else f", next scale {gs / 16:g}"))
+            self.last_step_overflowed = True
+            # GradScaler semantics: optimizer.step() must be a no-op for this step.  Gradients of None make torch optimisers skip the
+            # parameter entirely (no moment decay, no step count, no weight move); zeros would still move Adam's weights by its momentum.
+            return [None] * len(pnames)
+        self.last_step_overflowed = False
+        # parameters no kernel touched (frozen phase / unused) keep grad None; the others leave as accumulator x 1 / scale -- one multi-tensor
+        # launch set instead of one launch per parameter (290 with PSPNet, 1109 with HRNet-OCR; same fp32 products)
+        out = [None] * len(pnames)
+        idx = [i for i, k in enumerate(pnames) if getattr(rt["P"][k], "gacc_touched", False)]
+        if idx:
+            for i, g in zip(idx, torch._foreach_mul([rt["P"][pnames[i]].gacc for i in idx], inv)):
+                out[i] = g
+        return out
+
+
+class JointModelWithLoss(_TrainBase):
+    def __init__(self, cfg, num_train_ds, resume_iter, sr_transforms=None, antialias=True, device="cuda:0", seed=None, pretrained_root="weights"):
+        super().__init__(cfg, antialias, device, seed, pretrained_root)
+        # bicubic: calc_sr_loss returns None before it looks at the loss function (build_model.py:163-166), so the keys that only shape
+        # KBPN or the SR loss have no effect, as in the reference (the list: DESIGN.md section 1.5); _JointBase's refusals of values no model
+        # of this build takes (SUM_LR_ERROR_POS, NUM_CLASSES, SR_SEG_INV, JOINT_LEARNING) hold for this model too
+        if cfg.SOLVER.SEG_LOSS_FUNC != "BoundaryCombo" or (cfg.SOLVER.SR_LOSS_FUNC != "KBPN" and not self.bicubic):
+            raise NotImplementedError("csbsr_amd builds SEG_LOSS_FUNC=BoundaryCombo with SR_LOSS_FUNC=KBPN")
+        if cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SS_AMP != 0 or cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0 or cfg.SOLVER.INTERM_SSLOSSWEGHT4SR:
+            raise NotImplementedError("oriented loss weights other than SEG_FAIL_ORIENTED_WEIGHT4SR are not built")
+        seg_rsm = resume_iter - (cfg.SOLVER.SR_PRETRAIN_ITER[1] - 1) if resume_iter > (cfg.SOLVER.SR_PRETRAIN_ITER[1] - 1) else 0
+        per_epoch = num_train_ds // cfg.SOLVER.BATCH_SIZE + 1
+        self.ss_loss_fn = BoundaryComboState(per_epoch, seg_rsm, decrease_ratio=cfg.SOLVER.BOUNDARY_DEC_RATIO)
+        self.sr_loss_fn = "KBPNLoss"
+        self.aux_weight, self.main_weight = cfg.SOLVER.SEG_AUX_LOSS_WEIGHT, cfg.SOLVER.SEG_MAIN_LOSS_WEIGHT
+        self.iter_cnt = True
+        self._init_loss_scale()
+        self.last_dsr = self.last_dkvec = None      # set by the backward of forward_from_sr (validation)
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, iter, x, sr_targets=None, segment_targets=None, kernel_targets=None, segment_sdf=None):
+        """``segment_sdf`` (optional, not in the reference's signature): the signed distance map of ``segment_targets`` already on the
+        device -- csbsr_amd.data.degrade.DeviceDegradation computes it with the batch -- so the loss does not recompute it."""
+        rt = self._runtime()
+        if self.bicubic:
+            # forward_sr's bicubic branch: sr_preds is the UNCLIPPED up-scaled input, kernel_preds zeros of the target's shape, sr_loss None;
+            # the detector and its loss are the kernels of the joint model's detector half on the same bytes
+            self._invalidate()
+            x, mask, kgt = self._mount(x), self._mount(segment_targets), self._mount(kernel_targets)
+            self._n_res = 0
+            return self._detector_and_losses(iter, x, None, mask, kgt, self._bicubic_up(x, clip=False), None, None, x.shape[0],
+                                             sdf=self._mount(segment_sdf), sr_terms=False)
+        eng, kbpn, psp, pc = rt["eng"], rt["kbpn"], rt["psp"], self.pc
+        kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
+        self._invalidate()              # master weights may have been stepped by the optimiser
+        x, hr, mask, kgt = self._mount(x), self._mount(sr_targets), self._mount(segment_targets), self._mount(kernel_targets)
+        sr32, kvec, saves, mb = self._kbpn_forward(iter, x, kgt)
         return self._detector_and_losses(iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=self._mount(segment_sdf))
 
     def forward_from_sr(self, iter, sr_preds, kernel_vec, x, sr_targets, segment_targets, kernel_targets):
@@ -484,73 +719,15 @@ class JointModelWithLoss(_JointBase):
                           psp_saved=psp_saved, detector_only=True)
                 seg_loss = _SegFn.apply(self, st, seg_loss, *[p for p in self.parameters()])
             return seg_loss, None, seg32, sr32, torch.zeros_like(kgt)
-        # KBPNLoss: L1(sr, hr), L1(down(blur(sr)), x), MSE(kernel) * 0
-        ksum = kvec.sum(1, keepdim=True)
-        vec = (kvec / ksum).contiguous()
-        K = pc.ksize_out
-        wmap = None
-        if iter > pc.oriented_w_iter and pc.oriented_w_iter != -1 and pc.sfo_sr_amp != 0:
-            wmap = torch.exp(pc.sfo_sr_amp * (seg32 - mask).abs()).contiguous()      # oriented_weight.py:73-83 (detached)
-        wmap_lr = None
-        if wmap is not None:
-            wmap_lr = eng.f32(B, 1, h, w, zero=False)
-            L.call("csbsr_bilinear32_fwd", _ptr(wmap), _ptr(wmap_lr), B, H, W, h, w, 0, eng.stream)
-        blurred = eng.f32(B, 3, H, W, zero=False)
-        L.call("csbsr_blur_fwd", _ptr(sr32), _ptr(vec), B, 3, H, W, K, 1, None, _ptr(blurred), None, 0, eng.stream)
-        lr_pred = eng.f32(B, 3, h, w, zero=False)
-        L.call("csbsr_aa_bicubic_down_fwd", _ptr(blurred), _ptr(lr_pred), B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
-        s_hr, s_lr = eng.f32(B), eng.f32(B)
-        L.call("csbsr_l1_fwd_bwd", _ptr(sr32), _ptr(hr), _ptr(wmap), B, 3, hw, _ptr(s_hr), 0.0, None, None, 0, eng.stream)
-        L.call("csbsr_l1_fwd_bwd", _ptr(lr_pred), _ptr(x), _ptr(wmap_lr), B, 3, h * w, _ptr(s_lr), 0.0, None, None, 0, eng.stream)
-        kpred = vec.reshape(B, 1, K, K)
-        k_l = ((kpred - kgt) ** 2).mean((1, 2, 3))
-        # SOLVER.ONLY_KERNEL_LOSS_FOR_PRETRAIN (sr_loss_functions.py:50-51): during the kernel-module pretraining phase the SR loss IS the
-        # kernel MSE (the reference returns the unreduced [B,1,K,K] map there and calc_loss takes its mean: the per-sample mean has the same mean)
-        sr_w = (0.0, 0.0, 1.0) if (pc.only_kernel_loss and pc.kernel_pretrain[0] <= iter < pc.kernel_pretrain[1]) else pc.sr_w
-        sr_loss = sr_w[0] * s_hr / (3 * hw) + sr_w[1] * s_lr / (3 * h * w) + sr_w[2] * k_l
-        del blurred
+        sr_loss, kpred, terms = self._sr_loss_terms(iter, x, hr, kgt, sr32, kvec, seg32, mask)
         if keep:
-            st = dict(iter=iter, x=x, hr=hr, mask=mask, kgt=kgt, sr32=sr32, kvec=kvec, ksum=ksum, vec=vec, mean=mean, invstd=invstd,
-                      seg32=seg32, aux32=aux32, sdf=sdf, sums_m=sums_m, sums_a=sums_a, alpha=alpha, lr_pred=lr_pred,
-                      wmap=wmap, wmap_lr=wmap_lr, saves=saves, mb=mb, B=B, h=h, w=w, psp_saved=psp_saved, n_res=self._n_res, sr_w=sr_w,
-                      pad_takes=getattr(self, "_pad_takes", None) if saves is not None else None)
+            st = dict(iter=iter, x=x, hr=hr, mask=mask, kgt=kgt, sr32=sr32, kvec=kvec, mean=mean, invstd=invstd,
+                      seg32=seg32, aux32=aux32, sdf=sdf, sums_m=sums_m, sums_a=sums_a, alpha=alpha,
+                      saves=saves, mb=mb, B=B, h=h, w=w, psp_saved=psp_saved, n_res=self._n_res,
+                      pad_takes=getattr(self, "_pad_takes", None) if saves is not None else None, **terms)
             params = [p for p in self.parameters()]
             seg_loss, sr_loss = _JointFn.apply(self, st, seg_loss, sr_loss, *params)
         return seg_loss, sr_loss, seg32, sr32, kpred
-
-    def _auto_resident(self, B, mb, H, W, agree=True):
-        """micro-batches whose KBPN activations fit next to the detector's working set (measured at HR 1792^2: 26.5 GB per image
-        of KBPN activations, 6.3 / 9.5 GB per image for PSPNet / HRNet-OCR incl. their backward workspaces -- the split-precision
-        detector holds two planes per activation) with 18 GB to spare.  The budget is what is FREE now (driver-reported free memory
-        plus what torch's caching allocator holds but does not use), so another tenant of the GPU or a second model in the process
-        lowers the residency instead of running the step out of memory; the rest is recomputed in the backward."""
-        r = (H * W) / float(1792 * 1792)
-        free, _ = torch.cuda.mem_get_info(self._device)
-        free += torch.cuda.memory_reserved(self._device) - torch.cuda.memory_allocated(self._device)
-        det = (9.5e9 if self.seg_model_name == "HRNet_OCR" else 6.3e9) * r * B
-        if self.detector_precision == "split":
-            det += 4.9e9 * r * B
-        n_mb = (B + mb - 1) // mb
-
-        def fit(per_img):
-            imgs = int((free - 18e9 - det) // (per_img * r)) if r > 0 else B
-            return max(0, min(n_mb, imgs // mb))
-        full, lean = fit(26.5e9), fit(21.2e9)      # lean saves: the kernel predictors' fe_SR chains are rebuilt in the backward (KBPN.forward)
-        if agree and self.reducer is not None and self.reducer.active:
-            # data-parallel: the ranks must take the SAME schedule (at ~240 of 288 GB the collective library's buffers can tip one rank into
-            # recomputing a KBPN forward, and every other rank would wait for it at the all-reduce): the minimum over the ranks, agreed
-            # in one tiny collective per problem shape.  EVERY rank must present each training shape (B, micro-batch, H, W) -- the
-            # data-parallel contract anyway: equal shards, train.py:105-112 of the reference -- and only training forwards with autograd
-            # on take part (``agree``); eval / no_grad forwards keep nothing resident and use the local figures.  The agreement is kept
-            # for the life of the model: renewing it when ONE rank's free memory drops later would be a collective only that rank enters
-            key = (B, mb, H, W, self.detector_precision)
-            agreed = self.__dict__.setdefault("_sched_agreed", {})
-            if key not in agreed:
-                agreed[key] = self.reducer.agree_min([full, lean])
-            full, lean = agreed[key]
-        if self.lean_saves is not None:
-            return (lean, True) if self.lean_saves else (full, False)
-        return (lean, True) if lean > full else (full, False)
 
     # ------------------------------------------------------------------ backward
     def _hip_backward(self, st, dseg_loss, dsr_loss):
@@ -604,96 +781,73 @@ class JointModelWithLoss(_JointBase):
             psp.saved = None
             if self.blur_skip or detector_only:
                 return self._finish_backward(pnames, gs, (), st)
-        # ---- SR loss gradients
-        dkvec = eng.f32(B, pc.ksize_out ** 2)
-        if dsr_loss is not None:
-            g = (dsr_loss.to(torch.float32) * gs)
-            K = pc.ksize_out
-            sr_w = st["sr_w"]
-            g_hr = (g * sr_w[0] / (3 * hw)).contiguous()
-            g_lr = (g * sr_w[1] / (3 * h * w)).contiguous()
-            L.call("csbsr_l1_fwd_bwd", _ptr(st["sr32"]), _ptr(st["hr"]), _ptr(st["wmap"]), B, 3, hw, None, 1.0, _ptr(g_hr), _ptr(dsr32), 1,
-                   eng.stream)
-            dlr = eng.f32(B, 3, h, w, zero=False)
-            L.call("csbsr_l1_fwd_bwd", _ptr(st["lr_pred"]), _ptr(st["x"]), _ptr(st["wmap_lr"]), B, 3, h * w, None, 1.0, _ptr(g_lr), _ptr(dlr), 0,
-                   eng.stream)
-            dbl = eng.f32(B, 3, H, W, zero=False)
-            L.call("csbsr_aa_bicubic_down_bwd", _ptr(dlr), _ptr(dbl), 0, B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
-            L.call("csbsr_blur_bwd_input", _ptr(dbl), _ptr(st["vec"]), _ptr(dsr32), 1, B, 3, H, W, K, 1, eng.stream)
-            dvec = eng.f32(B, K * K)
-            L.call("csbsr_blur_bwd_kernel", _ptr(dbl), _ptr(st["sr32"]), _ptr(dvec), B, 3, H, W, K, 1, eng.stream)
-            if sr_w[2] != 0:
-                dvec += (g * sr_w[2] / (K * K)).reshape(B, 1) * 2 * (st["vec"] - st["kgt"].reshape(B, -1))
-            dkvec = (dvec - (dvec * st["vec"]).sum(1, keepdim=True)) / st["ksum"]
-            del dbl, dlr
+        dkvec = self._sr_loss_seed(st, dsr_loss, gs, dsr32)
         # ---- KBPN backward (per micro-batch; recompute the forward when it was not kept)
-        mb = st["mb"]
-        saves = st["saves"]
-        if saves is None:        # forward_from_sr: the graph ends at the given SR image
+        if st["saves"] is None:        # forward_from_sr: the graph ends at the given SR image
             self.last_dsr, self.last_dkvec = dsr32 / gs, dkvec / gs
             return self._finish_backward(pnames, gs, ("segmentation_model",) if seg_active else (), st)
-        order = list(enumerate(range(0, B, mb)))
-        # resident micro-batches last-in first-out (frees HBM before the recomputed ones run), then the rest with their forward
-        # recomputed here (KBPN has no batch-coupled op: exact)
-        sched = [(i, b0, False) for i, b0 in reversed(order) if saves[i] is not None] + [(i, b0, True) for i, b0 in order if i >= st["n_res"]]
-        launched = set()
-
-        def stage_done(s):      # last micro-batch only: stage s's parameter gradients are final -> exchange them under the rest
-            if self.reducer is not None:
-                self.reducer.launch_flat(rt["flat"].get(f"kbpn.{s}"))
-                launched.add(f"kbpn.{s}")
-        for j, (i, b0, recompute) in enumerate(sched):
-            if recompute:
-                kbpn.forward(st["x"][b0:b0 + mb], st["iter"], st["kgt"][b0:b0 + mb], save=True,
-                             pad_replay=st["pad_takes"][i] if kbpn.zero_pad else None)
-            else:
-                kbpn.saved, saves[i] = saves[i], None
-            kbpn.backward(dsr32[b0:b0 + mb].contiguous(), dkvec[b0:b0 + mb].contiguous(),
-                          stage_done=stage_done if j == len(sched) - 1 else None)
-        st["kbpn_launched"] = launched
+        st["kbpn_launched"] = self._kbpn_backward_schedule(st, dsr32, dkvec)
         return self._finish_backward(pnames, gs, ("sr_model",), st)
 
-    def _finish_backward(self, pnames, gs, reduce_groups, st):
-        rt = self._rt
-        rt["eng"].join_wgrad()
-        if self.reducer is not None:
-            # whatever this phase's backward wrote and has not been launched yet (every rank takes the same branch: the set of
-            # buckets depends on the training phase only)
-            for b, flat in rt["flat"].items():
-                grp = "segmentation_model" if b == "seg" else "sr_model"
-                if grp in reduce_groups and not (b == "seg" and st.get("seg_launched")) and b not in st.get("kbpn_launched", ()):
-                    self.reducer.launch_flat(flat)
-            self.reducer.finish()
-        inv = 1.0 / gs
-        # overflow check on the (already all-reduced, so rank-consistent) accumulators: one scalar read back per step
-        finite = bool(torch.isfinite(torch.stack(torch._foreach_norm(list(rt["flat"].values()))).sum()))
-        if not finite:
-            self.overflow_steps += 1
-            if self.grad_scale is None:
-                self.scale_backoff += 4
-            import warnings
-            warnings.warn(f"csbsr_amd: fp16 gradient overflow at loss scale {gs:g}; this step is skipped (every gradient is None)"
-                          + ("" if self.grad_scale is not None else f", next scale {gs / 16:g}"))
-            self.last_step_overflowed = True
-            # GradScaler semantics: optimizer.step() must be a no-op for this step.  Gradients of None make torch optimisers skip the
-            # parameter entirely (no moment decay, no step count, no weight move); zeros would still move Adam's weights by its momentum.
-            return [None] * len(pnames)
-        self.last_step_overflowed = False
-        # parameters no kernel touched (frozen phase / unused) keep grad None; the others leave as accumulator x 1 / scale -- one multi-tensor
-        # launch set instead of one launch per parameter (290 with PSPNet, 1109 with HRNet-OCR; same fp32 products)
-        out = [None] * len(pnames)
-        idx = [i for i, k in enumerate(pnames) if getattr(rt["P"][k], "gacc_touched", False)]
-        if idx:
-            for i, g in zip(idx, torch._foreach_mul([rt["P"][pnames[i]].gacc for i in idx], inv)):
-                out[i] = g
-        return out
+
+class SRModelWithLoss(_TrainBase):
+    """KBPN and KBPNLoss alone (build_model.py:535-552): the model of the reference's ``DATASET.ONLY_IMAGES`` regime, whose run leaves the
+    weights every ``MODEL.SR_SCRATCH = False`` model starts from (``pretrained_sr_path``).
+
+        .forward(iter, x, sr_targets=None, kernel_targets=None) -> (sr_loss[B], sr_preds[B,3,H,W], kernel_preds[B,1,K,K])
+
+    It holds ``sr_model.*`` only: ``state_dict()`` and ``parameters()`` are the ``sr_model.*`` part of the joint model's, in its order, and no
+    detector is constructed, moved to the device or given a gradient bucket.  The forward and the backward are the joint model's SR half
+    (_TrainBase): the same launches on the same bytes, so inside ``SR_PRETRAIN_ITER`` the two models produce the same bits.  The loss scale
+    follows the PSPNet rule, 2^round(log2(B*H*W)) minus ``scale_backoff``, and the residency budget has no detector term."""
+
+    def __init__(self, cfg, sr_transforms=None, num_train_ds=None, resume_iter=None, antialias=True, device="cuda:0", seed=None,
+                 pretrained_root="weights"):
+        if cfg.SOLVER.SR_LOSS_FUNC != "KBPN":
+            raise NotImplementedError(f"SOLVER.SR_LOSS_FUNC={cfg.SOLVER.SR_LOSS_FUNC!r}: csbsr_amd builds KBPNLoss")
+        if cfg.SOLVER.ORIENTED_WEIGHT_ITER != -1 and (cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SR_AMP != 0 or cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0):
+            # sr_loss_functions.py hands segment_preds=None to the oriented weight there: the reference fails at the first such iteration
+            raise NotImplementedError("an oriented SR-loss weight needs the detector's map, which the SR-only model does not have")
+        super().__init__(cfg, antialias, device, seed, pretrained_root, sr_only=True)
+        self.sr_loss_fn = "KBPNLoss"
+        self._init_loss_scale()
+
+    def forward(self, iter, x, sr_targets=None, kernel_targets=None):
+        rt = self._runtime()
+        kbpn = rt["kbpn"]
+        kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
+        self._invalidate()              # master weights may have been stepped by the optimiser
+        x, hr, kgt = self._mount(x), self._mount(sr_targets), self._mount(kernel_targets)
+        B, _, h, w = x.shape
+        sr32, kvec, saves, mb = self._kbpn_forward(iter, x, kgt)
+        sr_loss, kpred, terms = self._sr_loss_terms(iter, x, hr, kgt, sr32, kvec, None, None)
+        if self.training and torch.is_grad_enabled():
+            st = dict(iter=iter, x=x, hr=hr, kgt=kgt, sr32=sr32, kvec=kvec, saves=saves, mb=mb, B=B, h=h, w=w, n_res=self._n_res,
+                      pad_takes=self._pad_takes, **terms)
+            sr_loss = _SRFn.apply(self, st, sr_loss, *[p for p in self.parameters()])
+        return sr_loss, sr32, kpred
+
+    def _hip_backward(self, st, dsr_loss):
+        rt, pc = self._rt, self.pc
+        eng = rt["eng"]
+        B, H, W = st["B"], st["h"] * pc.scale, st["w"] * pc.scale
+        gs = self.grad_scale or float(2 ** (round(math.log2(B * H * W)) - self.scale_backoff))      # the PSPNet rule of the joint model
+        eng.grad_scale = gs
+        pnames = [k for k, v in self._named_full() if isinstance(v, nn.Parameter)]     # == self.parameters() order
+        for k in pnames:                    # fresh fp32 accumulators for this backward
+            rt["P"][k].gacc_touched = False
+        torch._foreach_zero_(list(rt["flat"].values()))
+        dsr32 = eng.f32(B, 3, H, W)
+        dkvec = self._sr_loss_seed(st, dsr_loss, gs, dsr32)
+        st["kbpn_launched"] = self._kbpn_backward_schedule(st, dsr32, dkvec)
+        return self._finish_backward(pnames, gs, ("sr_model",), st)
 
 
 class JointModel(_JointBase):
     """Inference counterpart (build_model.py:441-500): SR clipped to [0,1] before segmentation, kernel normalised."""
 
-    def __init__(self, cfg, antialias=True, device="cuda:0", seed=None):
-        super().__init__(cfg, antialias, device, seed)
+    def __init__(self, cfg, antialias=True, device="cuda:0", seed=None, pretrained_root="weights"):
+        super().__init__(cfg, antialias, device, seed, pretrained_root)
         self.ksize = cfg.BLUR.KERNEL_SIZE_OUTPUT
 
     @torch.no_grad()

@@ -23,8 +23,19 @@ of all-reduce) that the replicas hold the same bits -- at the start and again be
 losses and validation results are those of the GLOBAL batch.  With ``DeviceTrainLoader(shard_mode="batch")`` the run is the single-GPU run
 with the same global batch, and its checkpoints continue on another number of GPUs (``resume``).
 
-Out of scope: the first-batch PNG dumps of trainer.py:186-227, ``do_pretrain_sr`` / ``SRModelWithLoss``, and every cfg value the model
-constructors refuse (they keep raising there).
+SR-only pretraining (the reference's ``DATASET.ONLY_IMAGES`` regime, train.py:70-74, 114-115 and trainer.py:252-402): ``do_pretrain_sr``
+and ``validate_sr`` drive an ``SRModelWithLoss`` over an image-only ``DeviceTrainLoader`` (batches of ``(x, hr, k)``) with the same rules --
+device-side fp64 window sum, one read-back per ``log_step``, the three checkpoint files, exact ``resume`` -- and ``export_pretrained_sr``
+writes the file every ``MODEL.SR_SCRATCH = False`` model starts from.
+
+    model = SRModelWithLoss(cfg)
+    optimizer = build_optimizer(cfg, model)
+    scheduler = build_scheduler(cfg, optimizer, resume_iter, scheduler_flag=False)       # train.py:74: constant rate in this regime
+    do_pretrain_sr(cfg, model, optimizer, scheduler, train_loader, eval_loader, resume_iter=resume_iter, output_dir=out)
+    export_pretrained_sr(model, cfg)
+
+Out of scope: the first-batch PNG dumps of trainer.py:186-227 and :355-386, data-parallel SR pretraining (``do_pretrain_sr`` refuses it), and
+every cfg value the model constructors refuse (they keep raising there).
 """
 import datetime
 import os
@@ -105,9 +116,11 @@ def build_optimizer(cfg, model):
     raise NotImplementedError(f"MODEL.OPTIMIZER={cfg.MODEL.OPTIMIZER!r}: 'Adam' or 'SGD'")
 
 
-def build_scheduler(cfg, optimizer, resume_iter=0):
-    """train.py:95-96.  Build it AFTER ``resume``: LambdaLR counts from 0 again and ``resume_iter`` is its offset."""
-    return LambdaLR(optimizer, lr_lambda=UpDownScheduler(cfg.SOLVER.SR_PRETRAIN_ITER[1], resume_iter, cfg.SOLVER.SCHEDULER))
+def build_scheduler(cfg, optimizer, resume_iter=0, scheduler_flag=None):
+    """train.py:95-96.  Build it AFTER ``resume``: LambdaLR counts from 0 again and ``resume_iter`` is its offset.  ``scheduler_flag``
+    None takes ``SOLVER.SCHEDULER``; the SR-only regime passes False whatever the config says (train.py:74)."""
+    flag = cfg.SOLVER.SCHEDULER if scheduler_flag is None else bool(scheduler_flag)
+    return LambdaLR(optimizer, lr_lambda=UpDownScheduler(cfg.SOLVER.SR_PRETRAIN_ITER[1], resume_iter, flag))
 
 
 # ------------------------------------------------------------------------------------------------------------------ logging
@@ -500,6 +513,128 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
             finally:
                 model.iter_cnt = True
             log({"iteration": iteration, **result, **names})
+
+        if after is not None:
+            after(iteration, model, record)
+
+
+# ------------------------------------------------------------------------------------------------------------------ SR-only pretraining
+def print_pretrain_line(record):
+    """The default ``log`` of ``do_pretrain_sr``: the reference's console lines (trainer.py:300, :326, :392-393)."""
+    if "checkpoint" in record:
+        print("=====> Save Checkpoint to {}".format(record["checkpoint"]))
+    elif "eval_sr_loss" in record:
+        print(f"\nestimation result (iter={record['iteration']}):")
+        print(f"=====> SR_Loss({record['sr_loss_func']}): {record['eval_sr_loss']:.6f} PSNR:{record['psnr']:.4f} SSIM:{record['ssim']:.4f} "
+              f"PSNR(Kernel):{record['kernel_psnr']:.4f}")
+    else:
+        print("===> Iter: {:07d}, LR: {:.5f}, Cost: {:.2f}s, Eta: {}, SR_Loss({}): {:.6f}".format(
+            record["iteration"], record["lr"], record["cost_s"], record["eta"], record["sr_loss_func"], record["sr_loss"]))
+
+
+def validate_sr(model, loader, iteration, *, seed=None):
+    """One pass over ``loader`` (batches of ``(x, hr, k)``) with an SR-only model in ``eval()`` under ``no_grad`` (trainer.py:328-393):
+    the SR loss averaged over BATCHES, PSNR, SSIM and kernel PSNR averaged over IMAGES with the SR image and the kernel clamped to [0, 1].
+    ``seed`` as in ``validate``; the model's mode is restored."""
+    from .utils.estimate_metrics import psnr_ssim
+    if seed is not None:
+        loader.gen.manual_seed(int(seed))
+    was_training = model.training
+    losses, metrics = [], {"psnr": [], "ssim": [], "kernel_psnr": []}
+    model.eval()
+    try:
+        with torch.no_grad():
+            for x, hr, k in loader:
+                sr_l, sr, kp = model(iteration, x, sr_targets=hr, kernel_targets=k)
+                ps, ss = psnr_ssim(sr.clamp(0, 1), hr)
+                kps, _ = psnr_ssim(kp.clamp(0, 1), k)
+                losses.append(torch.as_tensor(sr_l).float().mean())
+                for key, v in zip(metrics, (ps, ss, kps)):
+                    metrics[key].append(torch.as_tensor(v).float().reshape(-1))
+    finally:
+        model.train(was_training)
+    if not losses:
+        raise ValueError("validation saw no batch")
+    nb, n = len(losses), int(sum(v.numel() for v in metrics["psnr"]))
+    flat = torch.cat([torch.stack(losses)] + [torch.cat(metrics[key]) for key in metrics]).cpu().double().tolist()      # the one read-back
+    out = {"eval_sr_loss": sum(flat[:nb]) / nb}
+    for i, key in enumerate(metrics):
+        out[key] = sum(flat[nb + i * n:nb + (i + 1) * n]) / n
+    out["batches"], out["images"] = nb, n
+    return out
+
+
+def export_pretrained_sr(model_or_state_dict, cfg, root="weights"):
+    """Write ``<root>/pretrain/KBPN_pretrain_x{SCALE}_stage{S}[_bicubic{K}].pth`` -- the ``sr_model.*`` tensors of an SR-only or joint
+    model (or of a state_dict of one, ``module.`` prefixes dropped), which is what ``MODEL.SR_SCRATCH = False`` loads -- and return its path."""
+    from .modeling.build_model import pretrained_sr_path
+    sd = model_or_state_dict.state_dict() if hasattr(model_or_state_dict, "state_dict") else model_or_state_dict
+    sd = {k: v.detach().cpu().clone() for k, v in fix_model_state_dict(sd).items() if k.startswith("sr_model.")}
+    if not sd:
+        raise ValueError("no sr_model.* tensor to export")
+    path = pretrained_sr_path(cfg, root)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    torch.save(sd, path)
+    return path
+
+
+def do_pretrain_sr(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *, resume_iter=0, log_step=50, save_step=2000, eval_step=2000,
+                   output_dir=None, log=print_pretrain_line, hooks=None):
+    """Train an SR-only model over ``train_loader`` (any iterable of ``(x, hr, k)``), iterations counted from ``resume_iter + 1``.  Per
+    iteration (trainer.py:275-290): model.train(), zero_grad, forward, ``sr_loss.mean()``, backward, optimizer.step(), scheduler.step().
+    Build the scheduler with ``build_scheduler(..., scheduler_flag=False)``.  ``hooks`` as in ``do_train``.
+
+    Every ``log_step`` iterations ``log`` receives {iteration, lr, sr_loss, overflow_steps, cost_s, eta, sr_loss_func}; ``sr_loss`` is the
+    window mean, summed on the device in fp64 and read back there -- the loop's only read-back.  Checkpoints are ``save_checkpoint``'s
+    three files and ``resume`` continues the run exactly; every ``eval_step`` iterations, with an ``eval_loader``, ``validate_sr`` runs
+    and its result goes to ``log``.  Data-parallel pretraining is not built: NotImplementedError before anything touches the device."""
+    if _forced() or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        raise NotImplementedError("do_pretrain_sr is single-GPU: data-parallel SR pretraining is not built")
+    before, after = _hook(hooks, "before_step"), _hook(hooks, "after_step")
+    names = {"sr_loss_func": cfg.SOLVER.SR_LOSS_FUNC}
+    sums, overflowed = None, 0
+    carried = model.__dict__.pop("_resume_logging", None)
+    if carried is not None and carried[0] == resume_iter:
+        sums, overflowed = carried[1]["sums"].to(torch.float64), int(carried[1]["overflowed"])
+    try:
+        max_iter = len(train_loader) + resume_iter - int(getattr(train_loader, "produced", 0))
+    except TypeError:
+        max_iter = None
+    trained_time, tic, end = 0.0, time.time(), time.time()
+    for iteration, (x, hr, k) in enumerate(train_loader, resume_iter + 1):
+        if before is not None:
+            before(iteration, model)
+        model.train()
+        optimizer.zero_grad()
+        sr_loss = model(iteration, x, sr_targets=hr, kernel_targets=k.detach())[0].mean()
+        sr_loss.backward()
+        optimizer.step()
+        scheduler.step()
+        step_sums = sr_loss.detach().double().reshape(1)
+        sums = step_sums if sums is None else sums.to(step_sums.device) + step_sums
+        overflowed += bool(getattr(model, "last_step_overflowed", False))
+        del sr_loss, x, hr, k
+        trained_time += time.time() - end
+        end = time.time()
+
+        record = None
+        if iteration % log_step == 0:
+            sr_m = sums.tolist()[0] / log_step          # the one read-back of the window
+            eta = "?" if max_iter is None else str(datetime.timedelta(seconds=int(trained_time / (iteration - resume_iter)
+                                                                                  * (max_iter - iteration))))
+            record = {"iteration": iteration, "lr": optimizer.param_groups[0]["lr"], "sr_loss": sr_m, "overflow_steps": overflowed,
+                      "cost_s": time.time() - tic, "eta": eta, **names}
+            log(record)
+            sums = None
+            tic = time.time()
+
+        if output_dir is not None and iteration % save_step == 0:
+            paths = save_checkpoint(output_dir, iteration, model, optimizer, train_loader,
+                                    torch.zeros(1, dtype=torch.float64) if sums is None else sums, overflowed)
+            log({"iteration": iteration, "checkpoint": paths["model"], **paths})
+
+        if eval_loader is not None and iteration % eval_step == 0:
+            log({"iteration": iteration, **validate_sr(model, eval_loader, iteration), **names})
 
         if after is not None:
             after(iteration, model, record)
