@@ -121,7 +121,7 @@ class Engine:
         self.wg_stream = None
         self._ws_by_stream = {}
         self._zero_blk, self._zero_off, self._zero_key, self._zero_by_stream = None, 0, None, {}
-        self._probe_epoch = 0
+        self._probe_epoch, self._probes = 0, {}      # PReLU slope probes by device address (prelu_fold_ok)
         self.timing = None              # list of (kind, flops, bytes, start_event, end_event, layer, shape, kernel id, ...) when profiling is on
 
     def tic(self):           # start of a timed launch: its recorded start event, or None -- at the cost of this one test -- with profiling off
@@ -205,15 +205,20 @@ class Engine:
         starts an asynchronous copy into pinned host memory; a later call takes the value once the copy's event has completed (``query``,
         never ``synchronize``) and until then decides from the last completed value (one or two optimiser steps old: the threshold, 1e-3
         -- the reference's SFTLikeBlock starts these slopes at 0.01 --, is ten Adam steps of lr 1e-4 above zero); only the very first
-        call of a parameter reads synchronously.  ``new_step`` drops the probes of reloaded parameters."""
-        st = getattr(p, "_slope_probe", None)
+        call of a parameter reads synchronously.  ``new_step`` drops the probes of reloaded parameters.
+
+        The probes live in ``self._probes``, keyed by the slope's device address: whichever Python wrapper of the parameter a caller holds
+        (the runtime tensor here, the nn.Parameter in ``load_state_dict``) names the same probe.  An entry keeps its tensor alive, so the
+        address cannot pass to another tensor while the entry exists."""
+        key = p.data_ptr()
+        st = self._probes.get(key)
         if st is None:
             host = torch.empty(p.numel(), dtype=torch.float32, pin_memory=True)
             host.copy_(p.detach().reshape(-1).to(torch.float32))
             ok = bool(float(host.min()) > 1e-3)
-            p._slope_probe = [host, None, ok, self._probe_epoch]
+            self._probes[key] = [host, None, ok, self._probe_epoch, p]
             return ok
-        host, ev, ok, epoch = st
+        host, ev, ok, epoch, _ = st
         if ev is not None and ev.query():          # the copy started by an earlier call has landed: take its value (never wait for it)
             ok, ev = bool(float(host.min()) > 1e-3), None
         if ev is None and epoch != self._probe_epoch:      # at most one probe per optimiser step (Engine.new_step)
@@ -221,7 +226,7 @@ class Engine:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
             epoch = self._probe_epoch
-        p._slope_probe = [host, ev, ok, epoch]
+        st[1:4] = ev, ok, epoch
         return ok
 
     def new_step(self, params=()):
@@ -229,8 +234,7 @@ class Engine:
         dropped for re-assigned / reloaded parameters (``params``) and every live probe may issue one new asynchronous read"""
         self._probe_epoch += 1
         for p in params:
-            if hasattr(p, "_slope_probe"):
-                del p._slope_probe
+            self._probes.pop(p.data_ptr(), None)
 
     # ------------------------------------------------------------------ elementwise wrappers
     def epilogue_bwd(self, dout, out=None, act=L.ACT_NONE, slope=0.0, prelu=None, res=None, res2=None, res_mode=L.RES_NONE,

@@ -16,16 +16,18 @@ Underneath nothing is torch.nn: the forward hands raw device pointers to libcsbs
 and the two loss vectors are outputs of one torch.autograd.Function whose backward runs the hand-written HIP
 backward pass; PyTorch only owns memory, streams and the optimizer.
 """
-import ctypes as C
 import math
 import os
+import re
+import warnings
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from .. import _lib as L
 from ..config import path_config
-from ..engine import Engine, FM, grad_acc, _ptr
+from ..engine import Engine, _ptr
 from ..utils.misc import fix_model_state_dict
 from .kbpn import KBPN
 from .pspnet import PSPNet
@@ -123,6 +125,7 @@ def load_pretrained_sr(model, cfg, root="weights"):
     with torch.no_grad():
         for k, v in sd.items():
             own[k].copy_(v)
+    # (no slope probe to drop: this runs in the constructor, before the runtime and its engine exist -- see _JointBase.load_state_dict)
     return path
 
 
@@ -157,19 +160,22 @@ class _JointBase(nn.Module):
         self.norm_method = cfg.SOLVER.NORM_SR_OUTPUT
         self.seg_model_name = None if self.sr_only else cfg.MODEL.DETECTOR_TYPE
         self.blur_skip = self.seg_model_name == "PSPNet_BlurSkip"
+        # what the code below asks of these flags: is there a KBPN, is there a detector, does KBPN take gradients (BlurSkip freezes it)
+        self._has_kbpn, self._has_detector = not self.bicubic, not self.sr_only
+        self._kbpn_trains = self._has_kbpn and not self.blur_skip
         self._device = torch.device(device)
         shapes = joint_state_shapes(self.pc.scale, self.pc.num_stages, self.pc.ksize, self.pc.ksize_out, self.seg_model_name or "PSPNet",
                                     pixel_shuffle=self.pc.pixel_shuffle, kernel_sft=self.pc.kernel_sft, lr_error=self.pc.lr_error,
                                     zero_pad_kernel=self.pc.zero_pad_kernel)
         # registration order = reference state_dict order: segmentation_model.* then sr_model.*
-        self.segmentation_model = None if self.sr_only else _ParamGroup(shapes, "segmentation_model")
+        self.segmentation_model = _ParamGroup(shapes, "segmentation_model") if self._has_detector else None
         # (bicubic: the reference's ``sr_model`` is this string and its state_dict / parameters() hold the detector alone)
-        self.sr_model = "bicubic" if self.bicubic else _ParamGroup(shapes, "sr_model")
+        self.sr_model = _ParamGroup(shapes, "sr_model") if self._has_kbpn else "bicubic"
         gen = torch.Generator().manual_seed(cfg.SEED if seed is None else seed)
         for full, t in self._named_full():
             if t.is_floating_point() and not full.endswith(("running_mean", "running_var")):
                 _init_reference_style(full, t.data, gen)
-        if not self.bicubic and not cfg.MODEL.SR_SCRATCH:      # build_model.py:101-110; the detector's tensors keep the seeded init above
+        if self._has_kbpn and not cfg.MODEL.SR_SCRATCH:      # build_model.py:101-110; the detector's tensors keep the seeded init above
             self.pretrained_sr_path = load_pretrained_sr(self, cfg, pretrained_root)
         if self.blur_skip:        # build_model.py:352-368: everything but blur_skip.* is fixed
             for full, t in self._named_full():
@@ -184,50 +190,28 @@ class _JointBase(nn.Module):
         self.lean_saves = None        # None: lean KBPN saves (KBPN.forward) only when that keeps more micro-batches resident; True / False force it
         self.dropout_enabled = True
         self.dropout_masks = None     # tests may inject {name: [B,C] fp32} keep-masks
-        # Precision plan of the detector's FORWARD pass (PSPNet / PSPNet_BlurSkip / HRNet-OCR):
-        #   "split"  (default: the mode that meets north_star's 1e-3 on the segmentation output) activations and weights as fp16 hi + lo
-        #            pairs (~22 mantissa bits), three MFMA passes per conv into one fp32 accumulator -- the detector matches the fp32
-        #            reference to ~1e-4 on identical inputs where plain fp16 storage gives 3e-3 (contractive weights) .. 4e-2 (random
-        #            weights, a ~100x amplifier of every layer's rounding: DESIGN.md section 2).  Costs ~3x the detector's forward MFMA
-        #            time (~11 % of a config-2 step) and 2x its activation memory; the backward is unchanged (fp16 hi planes).
-        #   "fp16"   fp16 activation storage, one MFMA pass: the throughput configuration, reported beside the headline by bench.py.
+        # Precision of the detector's FORWARD pass: "split" (default) runs activations and weights as fp16 hi + lo pairs, three MFMA passes
+        # per conv into one fp32 accumulator; "fp16" is plain fp16 storage and one pass, the throughput configuration bench.py reports beside
+        # the headline.  The backward is the same in both.
         self.detector_precision = "split"
-        # Per-layer refinement of the split mode (the precision PLAN): an ordered list of (regex on the conv's parameter name, K blocks)
-        # -- 3 = full hi + lo product, 2 = hi + lo activation against the fp16 weight, 1 = plain fp16 operands (Conv.fwd_blocks); the
-        # first match wins, unmatched layers run 3 blocks.  Swept in round 4 on the reference's own SR images (scripts/study_split_plan.py,
-        # profiles/r04_split_plan_study.json): every group of the trunk needs all three blocks (layer 3 alone at two blocks: 2.2e-3 on the
-        # map); only the tail (up_1 .. final) and the PSP module stay under 1e-3 with two, each eating a third to a half of the margin for
-        # < 2 % of the step, so the default plan is None -- EXCEPT, since round 5, the four blur_skip conv0 / conv1 pairs of PSPNet_BlurSkip
-        # (64 -> 505 -> 64 at full HR resolution, 48 % of a config-5 step): with their fp16 weights rounded tap-sum-preservingly and the mean
-        # compensation on (engine.Conv._wq / _dc_bias: what a layer with fewer than three blocks gets) the two-block plan measures 2.36e-4 on
-        # the map against 2.10e-4 with three (nearest rounding: 4.99e-4; gradients median 1.4e-3 vs 9e-4, bound 3e-2) on the reference's own
-        # SR image -- inside 1e-3 with 4x margin -- for a third of those layers' forward MFMA time.  The same rounding does NOT rescue the
-        # BatchNorm'd trunk layers, which stay at three.  Round 6 (review item 6, scripts/study_split_plan.py --combos on tap-sum-rounded weights,
-        # profiles/r06_split_plan_combos.json): the decoder TAIL of PSPNet -- up_1, up_2, up_3, final: 35 ms of split forward convolutions per
-        # config-2 step -- at two blocks together measures 4.15e-4 on the reference's own SR image against 7.9e-5 with three (up_2 1.7e-4, up_3
-        # 1.1e-4, final 3.0e-4, up_1 3.6e-4 alone; gradients median 1.14e-2 vs 1.03e-2, max 2.24e-2, bound 3e-2): inside the review's "sum
-        # <= 6e-4" criterion, and adopted; the PSP module on top of it (6.7e-4) is not.
-        # ``detector_hp_dgrad``: dgrads against [w_hi | w_lo] (two K blocks).  The same sweep shows it buys nothing -- every detector
-        # gradient tensor and dLoss/dSR agree with the reference equally well without it (PSPNet median 1.15e-2 vs 1.12e-2, HRNet-OCR
-        # 1.65e-2 both, BlurSkip 9.4e-4 vs 9.1e-4: the error is the ReLU-gate flips of the forward, not the weights' rounding) -- so it is off.
-        # BlurSkip's two conv blocks between the SFT layers (blur_skip.1 / .3: 64 -> 64 at full resolution, BatchNorm'd) join the plan in round 6:
-        # 2.36e-4 -> 3.79e-4 on the map, gradients unchanged (median 1.5e-3, max 3.6e-3; scripts/study_split_plan.py --combos,
-        # profiles/r06_split_plan_combos.json); the decoder tail on top of that measures 8.8e-4 on this detector and stays at three.
+        # ``detector_plan`` refines the split mode per layer: an ordered list of (regex on the conv's parameter name, K blocks) -- 3 = full
+        # hi + lo product, 2 = hi + lo activation against the fp16 weight, 1 = plain fp16 operands (Conv.fwd_blocks); the first match wins and
+        # unmatched layers run 3.  Two blocks go to BlurSkip's blur_skip layers and to PSPNet's decoder tail (up_1 .. final); every other
+        # layer keeps three.  ``detector_hp_dgrad`` runs dgrads against [w_hi | w_lo]; it is off.  The sweeps behind each choice: DESIGN.md section 2.
         self.detector_plan = [(r"blur_skip\.[02]\.conv_(scale|shift)\.[01]\.|blur_skip\.[13]\.layer", 2)] if self.blur_skip else None
-        if self.seg_model_name == "PSPNet" and __import__("os").environ.get("CSBSR_DEC_PLAN", "1") != "0":
+        if self.seg_model_name == "PSPNet" and os.environ.get("CSBSR_DEC_PLAN", "1") != "0":
             self.detector_plan = [(r"\.(up_[123]|final)\.", 2)]
-        if __import__("os").environ.get("CSBSR_BS_PLAN") == "0":        # (A/B hook: three blocks everywhere)
+        if os.environ.get("CSBSR_BS_PLAN") == "0":        # (A/B hook: three blocks everywhere)
             self.detector_plan = None
-        self.detector_hp_dgrad = __import__("os").environ.get("CSBSR_HP_DGRAD") == "1"      # (A/B hook; default off)
+        self.detector_hp_dgrad = os.environ.get("CSBSR_HP_DGRAD") == "1"      # (A/B hook; default off)
 
     # ---- naming: state_dict keys are the reference's dotted names
     def _named_full(self):
-        for grp in ("sr_model",) if self.sr_only else ("segmentation_model",) if self.bicubic else ("segmentation_model", "sr_model"):
-            for local, t in getattr(self, grp).named_local():
+        for grp, has in (("segmentation_model", self._has_detector), ("sr_model", self._has_kbpn)):
+            for local, t in getattr(self, grp).named_local() if has else ():
                 yield f"{grp}.{local}", t
 
     def state_dict(self, *a, **kw):
-        from collections import OrderedDict
         return OrderedDict((k, v.detach() if isinstance(v, nn.Parameter) else v) for k, v in self._named_full())
 
     def load_state_dict(self, sd, strict=True):
@@ -242,7 +226,8 @@ class _JointBase(nn.Module):
                     own[k].copy_(v)
         if self._rt is not None:
             self._invalidate()
-            self._rt["eng"].new_step([own[k] for k in sd if k in own])      # slope probes of the weights just replaced are stale
+            # slope probes of the weights just replaced are stale (the engine finds them by address, so the nn.Parameter names them)
+            self._rt["eng"].new_step([own[k] for k in sd if k in own])
         return missing, unexpected
 
     # ---- runtime (engine + layer objects) is built lazily on the device
@@ -253,8 +238,9 @@ class _JointBase(nn.Module):
             self.to(self._device)
             eng = Engine(self._device)
             P = {k: (v.data if isinstance(v, nn.Parameter) else v) for k, v in self._named_full()}
-            self._rt = {"eng": eng, "P": P, "kbpn": None if self.bicubic else KBPN(eng, P, self.pc), "psp": None if self.sr_only else HRNetOCR(eng, P)
-                        if self.seg_model_name == "HRNet_OCR" else PSPNet(eng, P, blur_dim=self.pc.ksize_out ** 2 if self.blur_skip else None)}
+            psp = None if not self._has_detector else HRNetOCR(eng, P) if self.seg_model_name == "HRNet_OCR" else \
+                PSPNet(eng, P, blur_dim=self.pc.ksize_out ** 2 if self.blur_skip else None)
+            self._rt = {"eng": eng, "P": P, "kbpn": KBPN(eng, P, self.pc) if self._has_kbpn else None, "psp": psp}
             self._make_grad_buckets()
         if self._rt["psp"] is None:        # SR-only: no detector, so no detector precision plan to apply
             return self._rt
@@ -262,7 +248,6 @@ class _JointBase(nn.Module):
             raise ValueError(f"detector_precision must be 'fp16' or 'split', got {self.detector_precision!r}")
         split = self.detector_precision == "split"
         self._rt["psp"].split = split
-        import re
         plan = [(re.compile(pat), int(nb)) for pat, nb in (self.detector_plan or ())]
         for c in self._rt["psp"].all_convs():      # the split mode's dgrads run against fp16 hi + lo weight pairs (Conv.bwd_input)
             c.hp_dgrad = split and bool(self.detector_hp_dgrad)
@@ -299,6 +284,7 @@ class _JointBase(nn.Module):
                 t.gacc_touched = False
                 off[b] += v.numel()
         rt["flat"] = flats
+        rt["pnames"] = [k for k, v in self._named_full() if isinstance(v, nn.Parameter)]     # == self.parameters() order
 
     def _invalidate(self):
         rt = self._rt
@@ -311,6 +297,15 @@ class _JointBase(nn.Module):
     # ---- shared forward pieces
     def _mount(self, t):
         return None if t is None else t.to(self._device, torch.float32).contiguous()
+
+    def _begin(self, *tensors):
+        """The start of every forward: KBPN's mode flags where there is a KBPN, a new engine step (the optimiser may have stepped the master
+        weights) and the batch on the device as contiguous fp32."""
+        kbpn = self._runtime()["kbpn"]
+        if kbpn is not None:
+            kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
+        self._invalidate()
+        return [self._mount(t) for t in tensors]
 
     def _instnorm_stats(self, sr32):
         eng = self._rt["eng"]
@@ -344,58 +339,22 @@ class _JointBase(nn.Module):
         return sr32
 
 
-class _JointFn(torch.autograd.Function):
-    """(segment_loss[B], sr_loss[B]) = f(parameters); backward = the HIP backward pass."""
+class _StepFn(torch.autograd.Function):
+    """(segment_loss[B], sr_loss[B]) = f(parameters), either of them None in a model that does not have it; backward = the HIP backward pass."""
 
     @staticmethod
     def forward(ctx, model, st, seg_loss, sr_loss, *params):
         ctx.model, ctx.st = model, st          # the saved state travels with THIS graph: a later forward cannot clobber it
         ctx.set_materialize_grads(False)       # an unused loss vector arrives as None, not as a zero tensor to be scanned
-        return seg_loss.clone(), sr_loss.clone()
+        return tuple(None if v is None else v.clone() for v in (seg_loss, sr_loss))
 
     @staticmethod
     def backward(ctx, dseg, dsr):
         st, ctx.st = ctx.st, None
         if st is None:
             raise RuntimeError("csbsr_amd: backward called twice on the same forward (activations are freed by the first backward)")
-        grads = ctx.model._hip_backward(st, dseg, dsr)
-        return (None, None, None, None) + tuple(grads)
-
-
-class _SegFn(torch.autograd.Function):
-    """segment_loss[B] = f(detector parameters) of the MODEL.SR="bicubic" model; backward = the detector half of the HIP backward pass."""
-
-    @staticmethod
-    def forward(ctx, model, st, seg_loss, *params):
-        ctx.model, ctx.st = model, st
-        ctx.set_materialize_grads(False)
-        return seg_loss.clone()
-
-    @staticmethod
-    def backward(ctx, dseg):
-        st, ctx.st = ctx.st, None
-        if st is None:
-            raise RuntimeError("csbsr_amd: backward called twice on the same forward (activations are freed by the first backward)")
-        grads = ctx.model._hip_backward(st, dseg, None)
-        return (None, None, None) + tuple(grads)
-
-
-class _SRFn(torch.autograd.Function):
-    """sr_loss[B] = f(KBPN parameters) of SRModelWithLoss; backward = the SR half of the HIP backward pass."""
-
-    @staticmethod
-    def forward(ctx, model, st, sr_loss, *params):
-        ctx.model, ctx.st = model, st
-        ctx.set_materialize_grads(False)
-        return sr_loss.clone()
-
-    @staticmethod
-    def backward(ctx, dsr):
-        st, ctx.st = ctx.st, None
-        if st is None:
-            raise RuntimeError("csbsr_amd: backward called twice on the same forward (activations are freed by the first backward)")
-        grads = ctx.model._hip_backward(st, dsr)
-        return (None, None, None) + tuple(grads)
+        grads = tuple(ctx.model._hip_backward(st, dseg, dsr))
+        return (None,) * (len(ctx.needs_input_grad) - len(grads)) + grads
 
 
 class _TrainBase(_JointBase):
@@ -403,7 +362,7 @@ class _TrainBase(_JointBase):
     gradient seed, the KBPN backward schedule and the end of a backward (exchange, overflow skip, un-scaling)."""
 
     def _init_loss_scale(self):
-        self.grad_scale = None          # None: chosen per call as 2^round(log2(B*H*W)) (see _hip_backward)
+        self.grad_scale = None          # None: chosen per call as 2^round(log2(B*H*W)) (see _begin_backward)
         self.scale_backoff = 0          # log2 reduction of the automatic scale after overflowed steps
         self.overflow_steps = 0
         self.last_step_overflowed = False
@@ -420,7 +379,7 @@ class _TrainBase(_JointBase):
         # (the rank agreement inside _auto_resident is a collective: only a forward that will be followed by a backward takes part in it, so
         # a rank-0-only validation pass, an evaluator sharing the model or a no_grad call can never leave the other ranks waiting)
         n_res, lean = (self.max_resident, bool(self.lean_saves)) if self.max_resident is not None else self._auto_resident(B, mb, H, W, agree=keep)
-        if self.max_resident is None and keep and n_res == 0 and mb >= B and B >= 2 and not self.blur_skip:
+        if self.max_resident is None and keep and n_res == 0 and mb >= B and B >= 2 and self._kbpn_trains:
             # the whole batch as ONE micro-batch is all-or-nothing: when it does not fit (RCCL buffers, another tenant, fragmentation)
             # halve the micro-batch so that part of the batch stays resident instead of recomputing every KBPN forward in the backward.
             # n_res is the agreed minimum over the ranks, so every rank takes this branch (and its second agreement) together
@@ -429,12 +388,11 @@ class _TrainBase(_JointBase):
             if n2 > 0:
                 mb, n_res, lean = mb2, n2, lean2
         self._n_res, self._lean, self._mb_used = n_res, lean, mb
-        single = mb >= B
         sr32 = eng.f32(B, 3, H, W, zero=False)
         kvec = eng.f32(B, pc.ksize_out ** 2, zero=False)
         saves, self._pad_takes = [], []
         for i, b0 in enumerate(range(0, B, mb)):
-            resident = keep and i < n_res and not self.blur_skip     # BlurSkip: KBPN is frozen, no backward through it
+            resident = keep and i < n_res and self._kbpn_trains      # BlurSkip: KBPN is frozen, no backward through it
             s_, k_ = kbpn.forward(x[b0:b0 + mb], iter, kgt[b0:b0 + mb], save=resident, lean=lean)
             saves.append(kbpn.saved if resident else None)
             self._pad_takes.append(kbpn.pad_taken)        # ZERO_PAD_KERNEL: a recomputed forward replays these (KBPN.forward)
@@ -486,11 +444,11 @@ class _TrainBase(_JointBase):
         r = (H * W) / float(1792 * 1792)
         free, _ = torch.cuda.mem_get_info(self._device)
         free += torch.cuda.memory_reserved(self._device) - torch.cuda.memory_allocated(self._device)
-        det = (9.5e9 if self.seg_model_name == "HRNet_OCR" else 6.3e9) * r * B
-        if self.detector_precision == "split":
-            det += 4.9e9 * r * B
-        if self.sr_only:        # no detector: its working set is KBPN's to keep
-            det = 0.0
+        det = 0.0               # no detector: its working set is KBPN's to keep
+        if self._has_detector:
+            det = (9.5e9 if self.seg_model_name == "HRNet_OCR" else 6.3e9) * r * B
+            if self.detector_precision == "split":
+                det += 4.9e9 * r * B
         n_mb = (B + mb - 1) // mb
 
         def fit(per_img):
@@ -512,6 +470,84 @@ class _TrainBase(_JointBase):
         if self.lean_saves is not None:
             return (lean, True) if self.lean_saves else (full, False)
         return (lean, True) if lean > full else (full, False)
+
+    def _saved_state(self, iter, x, det=None, hr=None, kgt=None, sr32=None, kvec=None, saves=None, mb=None, terms=None):
+        """What one backward needs, carried by its autograd node: the detector's part (``det``, _detector_and_losses) where there is a
+        detector and, with ``terms`` (_sr_loss_terms), the SR half's -- what _sr_loss_seed and the KBPN schedule read.  ``saves`` None:
+        the graph ends at a given SR image (forward_from_sr)."""
+        B, _, h, w = x.shape
+        st = dict(iter=iter, B=B, h=h, w=w, saves=saves, **(det or {}))
+        if terms is not None:
+            st.update(x=x, hr=hr, kgt=kgt, sr32=sr32, kvec=kvec, mb=mb, n_res=self._n_res,
+                      pad_takes=self._pad_takes if saves is not None else None, **terms)
+        return st
+
+    def _begin_backward(self, npix, backoff=True):
+        """The start of every backward -> (loss scale, parameter names in ``parameters()`` order): sets the engine's scale and hands the
+        kernels fresh fp32 accumulators.
+
+        The loss scale of the fp16 activation gradients: the per-pixel loss gradient is O(1/(B*H*W)), ``npix``; PSPNet keeps that magnitude
+        down to the input, HRNet-OCR grows it ~1e5x towards the stem (measured, reference-style init), so it starts 2^8 lower.
+        ``scale_backoff`` is the dynamic part (GradScaler semantics): a backward that overflowed returns no gradients for that step and
+        lowers the scale for the following ones.  ``grad_scale`` overrides all of it.  ``backoff=False`` (kbpn_backward_from, whose
+        upstream gradient is given) is 2^round(log2(npix)) whatever the model's state."""
+        rt = self._rt
+        e = round(math.log2(npix))
+        gs = float(2 ** e) if not backoff else \
+            self.grad_scale or float(2 ** (e - (8 if self.seg_model_name == "HRNet_OCR" else 0) - self.scale_backoff))
+        rt["eng"].grad_scale = gs
+        for k in rt["pnames"]:
+            rt["P"][k].gacc_touched = False
+        torch._foreach_zero_(list(rt["flat"].values()))      # the accumulators are views of a handful of flat buckets
+        return gs, rt["pnames"]
+
+    def _hip_backward(self, st, dseg_loss, dsr_loss):
+        """The backward of every model: the detector half where there is a detector and the caller's scalar used the segmentation loss,
+        then the KBPN half where KBPN takes gradients and the graph did not end at a given SR image."""
+        rt, pc = self._rt, self.pc
+        eng, psp = rt["eng"], rt["psp"]
+        B, h, w = st["B"], st["h"], st["w"]
+        H, W = h * pc.scale, w * pc.scale
+        hw = H * W
+        gs, pnames = self._begin_backward(B * hw)
+        dsr32 = eng.f32(B, 3, H, W) if self._has_kbpn else None      # (bicubic: the input is no function of a parameter)
+        # which halves of the backward run follows from which loss vector the caller's scalar loss used (autograd hands None for an
+        # unused output): a function of the training phase, identical on every rank, and no device read-back
+        seg_active = self._has_detector and dseg_loss is not None
+        if self._has_detector:
+            psp.saved = st["psp_saved"] if seg_active else None
+        if seg_active:
+            gsc = (dseg_loss.to(torch.float32) * gs).contiguous()
+            dseg32, daux32 = eng.f32(B, 1, H, W, zero=False), eng.f32(B, 1, H, W, zero=False)
+            pw, lw = pc.bce_w, pc.wbd_w
+            for p_, sums, wgt, dp in ((st["seg32"], st["sums_m"], self.main_weight, dseg32), (st["aux32"], st["sums_a"], self.aux_weight, daux32)):
+                L.call("csbsr_segloss_finish", _ptr(p_), _ptr(st["mask"]), _ptr(st["sdf"]), B, hw, _ptr(sums), st["alpha"], pw[0], pw[1],
+                       lw[0], lw[1], wgt, _ptr(gsc), None, _ptr(dp), 0, eng.stream)
+            dxin = psp.backward(dseg32, daux32, need_dxin=self._has_kbpn)      # (bicubic: no first-conv input gradient)
+            eng.join_wgrad()                    # the detector's weight gradients (side stream) are complete
+            if not self._kbpn_trains:           # bicubic, or BlurSkip where only blur_skip.* trains: no gradient leaves the segmentation net
+                return self._finish_backward(pnames, gs, ("segmentation_model",), st)
+            if self.reducer is not None:        # segmentation gradients are final: exchange them under the KBPN backward
+                self.reducer.launch_flat(rt["flat"].get("seg"))
+                st["seg_launched"] = True
+            if st["mean"] is not None and self.norm_method == "instance":
+                red = eng.f32(B * 3, 2)
+                L.call("csbsr_instnorm_bwd", _ptr(dxin.t), dxin.ld, _ptr(st["sr32"]), _ptr(st["mean"]), _ptr(st["invstd"]), _ptr(dsr32), 0,
+                       B, 3, hw, _ptr(red), eng.stream)
+            else:
+                eng.fm_to_nchw32(dxin, dsr32, 3)
+                if st["invstd"] is not None:
+                    dsr32 *= st["invstd"].reshape(B, 3, 1, 1)
+            del dxin, dseg32, daux32
+        elif not self._kbpn_trains:
+            return self._finish_backward(pnames, gs, (), st)
+        dkvec = self._sr_loss_seed(st, dsr_loss, gs, dsr32)
+        if st["saves"] is None:        # forward_from_sr: the graph ends at the given SR image
+            self.last_dsr, self.last_dkvec = dsr32 / gs, dkvec / gs
+            return self._finish_backward(pnames, gs, ("segmentation_model",) if seg_active else (), st)
+        # ---- KBPN backward (per micro-batch; recompute the forward when it was not kept)
+        st["kbpn_launched"] = self._kbpn_backward_schedule(st, dsr32, dkvec)
+        return self._finish_backward(pnames, gs, ("sr_model",), st)
 
     def _sr_loss_seed(self, st, dsr_loss, gs, dsr32):
         """Seeds of the KBPN backward from the SR loss: adds dLoss/d sr_preds (x ``gs``) into ``dsr32`` and returns dLoss/d kernel vector
@@ -587,7 +623,6 @@ class _TrainBase(_JointBase):
             self.overflow_steps += 1
             if self.grad_scale is None:
                 self.scale_backoff += 4
-            import warnings
             warnings.warn(f"csbsr_amd: fp16 gradient overflow at loss scale {gs:g}; this step is skipped (every gradient is None)"
                           + ("" if self.grad_scale is not None else f", next scale {gs / 16:g}"))
             self.last_step_overflowed = True
@@ -628,21 +663,15 @@ class JointModelWithLoss(_TrainBase):
     def forward(self, iter, x, sr_targets=None, segment_targets=None, kernel_targets=None, segment_sdf=None):
         """``segment_sdf`` (optional, not in the reference's signature): the signed distance map of ``segment_targets`` already on the
         device -- csbsr_amd.data.degrade.DeviceDegradation computes it with the batch -- so the loss does not recompute it."""
-        rt = self._runtime()
-        if self.bicubic:
+        x, hr, mask, kgt, sdf = self._begin(x, sr_targets if self._has_kbpn else None, segment_targets, kernel_targets, segment_sdf)
+        if self._has_kbpn:
+            sr32, kvec, saves, mb = self._kbpn_forward(iter, x, kgt)
+        else:
             # forward_sr's bicubic branch: sr_preds is the UNCLIPPED up-scaled input, kernel_preds zeros of the target's shape, sr_loss None;
             # the detector and its loss are the kernels of the joint model's detector half on the same bytes
-            self._invalidate()
-            x, mask, kgt = self._mount(x), self._mount(segment_targets), self._mount(kernel_targets)
             self._n_res = 0
-            return self._detector_and_losses(iter, x, None, mask, kgt, self._bicubic_up(x, clip=False), None, None, x.shape[0],
-                                             sdf=self._mount(segment_sdf), sr_terms=False)
-        eng, kbpn, psp, pc = rt["eng"], rt["kbpn"], rt["psp"], self.pc
-        kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
-        self._invalidate()              # master weights may have been stepped by the optimiser
-        x, hr, mask, kgt = self._mount(x), self._mount(sr_targets), self._mount(segment_targets), self._mount(kernel_targets)
-        sr32, kvec, saves, mb = self._kbpn_forward(iter, x, kgt)
-        return self._detector_and_losses(iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=self._mount(segment_sdf))
+            sr32, kvec, saves, mb = self._bicubic_up(x, clip=False), None, None, x.shape[0]
+        return self._detector_and_losses(iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=sdf)
 
     def forward_from_sr(self, iter, sr_preds, kernel_vec, x, sr_targets, segment_targets, kernel_targets):
         """Validation entry point: the detector + loss half of ``forward`` fed a GIVEN SR image [B,3,H,W] and (un-normalised) kernel
@@ -651,12 +680,9 @@ class JointModelWithLoss(_TrainBase):
         the SR image: its gradient (true scale) is left in ``self.last_dsr`` / ``self.last_dkvec``; KBPN parameters get no gradient."""
         if self.bicubic:
             raise NotImplementedError("forward_from_sr / kbpn_backward_from are entry points of the KBPN model; MODEL.SR='bicubic' has no SR loss")
-        rt = self._runtime()
-        self._invalidate()
-        x, hr, mask, kgt = self._mount(x), self._mount(sr_targets), self._mount(segment_targets), self._mount(kernel_targets)
-        sr32, kvec = self._mount(sr_preds), self._mount(kernel_vec).reshape(x.shape[0], -1)
+        x, hr, mask, kgt, sr32, kvec = self._begin(x, sr_targets, segment_targets, kernel_targets, sr_preds, kernel_vec)
         self._n_res = 0
-        return self._detector_and_losses(iter, x, hr, mask, kgt, sr32, kvec, None, x.shape[0])
+        return self._detector_and_losses(iter, x, hr, mask, kgt, sr32, kvec.reshape(x.shape[0], -1), None, x.shape[0])
 
     @torch.no_grad()
     def kbpn_backward_from(self, iter, x, kernel_targets, dsr, dkvec):
@@ -664,20 +690,12 @@ class JointModelWithLoss(_TrainBase):
         dLoss/d kernel vector [B,kk], true scale) -- e.g. the reference's own, from a golden fixture.  Returns {state_dict name: grad}."""
         if self.bicubic:
             raise NotImplementedError("forward_from_sr / kbpn_backward_from are entry points of the KBPN model; MODEL.SR='bicubic' has no KBPN")
-        rt = self._runtime()
-        eng, kbpn, pc = rt["eng"], rt["kbpn"], self.pc
-        kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
-        self._invalidate()
-        x, kgt, dsr, dkvec = self._mount(x), self._mount(kernel_targets), self._mount(dsr), self._mount(dkvec)
+        x, kgt, dsr, dkvec = self._begin(x, kernel_targets, dsr, dkvec)
+        rt, pc = self._rt, self.pc
+        eng, kbpn = rt["eng"], rt["kbpn"]
         B, _, h, w = x.shape
-        gs = float(2 ** round(math.log2(B * h * w * pc.scale * pc.scale)))
-        eng.grad_scale = gs
-        names = [k for k, v in self._named_full() if isinstance(v, nn.Parameter) and k.startswith("sr_model")]
-        for k in names:
-            t = rt["P"][k]
-            if getattr(t, "gacc", None) is not None:
-                t.gacc.zero_()
-            t.gacc_touched = False
+        gs, pnames = self._begin_backward(B * h * w * pc.scale * pc.scale, backoff=False)
+        names = [k for k in pnames if k.startswith("sr_model")]
         mb = max(1, min(self.micro_batch, B))
         for b0 in range(0, B, mb):
             kbpn.forward(x[b0:b0 + mb], iter, kgt[b0:b0 + mb], save=True)
@@ -685,7 +703,7 @@ class JointModelWithLoss(_TrainBase):
         eng.join_wgrad()
         return {k: (rt["P"][k].gacc / gs if getattr(rt["P"][k], "gacc_touched", False) else None) for k in names}
 
-    def _detector_and_losses(self, iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=None, sr_terms=True):
+    def _detector_and_losses(self, iter, x, hr, mask, kgt, sr32, kvec, saves, mb, sdf=None):
         rt, pc = self._rt, self.pc
         eng, psp = rt["eng"], rt["psp"]
         B, _, h, w = x.shape
@@ -713,81 +731,14 @@ class JointModelWithLoss(_TrainBase):
             L.call("csbsr_segloss_reduce", _ptr(p_), _ptr(mask), _ptr(sdf), B, hw, _ptr(sums), pw[0], pw[1], eng.stream)
             L.call("csbsr_segloss_finish", _ptr(p_), _ptr(mask), _ptr(sdf), B, hw, _ptr(sums), alpha, pw[0], pw[1], lw[0], lw[1], wgt,
                    None, _ptr(seg_loss), None, 0, eng.stream)
-        if not sr_terms:        # MODEL.SR="bicubic": no SR loss, and the graph ends at the detector's input
-            if keep:
-                st = dict(iter=iter, mask=mask, seg32=seg32, aux32=aux32, sdf=sdf, sums_m=sums_m, sums_a=sums_a, alpha=alpha, B=B, h=h, w=w,
-                          psp_saved=psp_saved, detector_only=True)
-                seg_loss = _SegFn.apply(self, st, seg_loss, *[p for p in self.parameters()])
-            return seg_loss, None, seg32, sr32, torch.zeros_like(kgt)
-        sr_loss, kpred, terms = self._sr_loss_terms(iter, x, hr, kgt, sr32, kvec, seg32, mask)
+        # MODEL.SR="bicubic": no SR loss (None, as the reference's), zeros for the kernel, and the graph ends at the detector's input
+        sr_loss, kpred, terms = self._sr_loss_terms(iter, x, hr, kgt, sr32, kvec, seg32, mask) if self._has_kbpn else (None, None, None)
         if keep:
-            st = dict(iter=iter, x=x, hr=hr, mask=mask, kgt=kgt, sr32=sr32, kvec=kvec, mean=mean, invstd=invstd,
-                      seg32=seg32, aux32=aux32, sdf=sdf, sums_m=sums_m, sums_a=sums_a, alpha=alpha,
-                      saves=saves, mb=mb, B=B, h=h, w=w, psp_saved=psp_saved, n_res=self._n_res,
-                      pad_takes=getattr(self, "_pad_takes", None) if saves is not None else None, **terms)
-            params = [p for p in self.parameters()]
-            seg_loss, sr_loss = _JointFn.apply(self, st, seg_loss, sr_loss, *params)
-        return seg_loss, sr_loss, seg32, sr32, kpred
-
-    # ------------------------------------------------------------------ backward
-    def _hip_backward(self, st, dseg_loss, dsr_loss):
-        rt, pc = self._rt, self.pc
-        eng, kbpn, psp = rt["eng"], rt["kbpn"], rt["psp"]
-        B, h, w = st["B"], st["h"], st["w"]
-        H, W = h * pc.scale, w * pc.scale
-        hw = H * W
-        # loss scale of the fp16 activation gradients: the per-pixel loss gradient is O(1/(B*H*W)); PSPNet keeps that magnitude down
-        # to the input, HRNet-OCR grows it ~1e5x towards the stem (measured, reference-style init), so it starts 2^8 lower.
-        # ``scale_backoff`` is the dynamic part (GradScaler semantics): a backward that overflowed returns zero gradients for that
-        # step and lowers the scale for the following ones.
-        gs = self.grad_scale or float(2 ** (round(math.log2(B * hw)) - (8 if self.seg_model_name == "HRNet_OCR" else 0) - self.scale_backoff))
-        eng.grad_scale = gs
-        pnames = [k for k, v in self._named_full() if isinstance(v, nn.Parameter)]     # == self.parameters() order
-        for k in pnames:                    # fresh fp32 accumulators for this backward
-            rt["P"][k].gacc_touched = False
-        torch._foreach_zero_(list(rt["flat"].values()))      # the accumulators are views of a handful of flat buckets
-        detector_only = bool(st.get("detector_only"))      # MODEL.SR="bicubic": the input is no function of a parameter
-        dsr32 = None if detector_only else eng.f32(B, 3, H, W)
-        # which halves of the backward run follows from which loss vector the caller's scalar loss used (autograd hands None for an
-        # unused output): a function of the training phase, identical on every rank, and no device read-back
-        seg_active = dseg_loss is not None
-        psp.saved = st["psp_saved"]
-        if seg_active:
-            gsc = (dseg_loss.to(torch.float32) * gs).contiguous()
-            dseg32, daux32 = eng.f32(B, 1, H, W, zero=False), eng.f32(B, 1, H, W, zero=False)
-            pw, lw = pc.bce_w, pc.wbd_w
-            for p_, sums, wgt, dp in ((st["seg32"], st["sums_m"], self.main_weight, dseg32), (st["aux32"], st["sums_a"], self.aux_weight, daux32)):
-                L.call("csbsr_segloss_finish", _ptr(p_), _ptr(st["mask"]), _ptr(st["sdf"]), B, hw, _ptr(sums), st["alpha"], pw[0], pw[1],
-                       lw[0], lw[1], wgt, _ptr(gsc), None, _ptr(dp), 0, eng.stream)
-            dxin = psp.backward(dseg32, daux32, need_dxin=not detector_only)
-            eng.join_wgrad()                    # the detector's weight gradients (side stream) are complete
-            if detector_only:                   # no first-conv input gradient, no csbsr_instnorm_bwd, no last_dsr
-                return self._finish_backward(pnames, gs, ("segmentation_model",), st)
-            if self.blur_skip:                  # only blur_skip.* trains: no gradient leaves the segmentation net
-                return self._finish_backward(pnames, gs, ("segmentation_model",), st)
-            if self.reducer is not None:        # segmentation gradients are final: exchange them under the KBPN backward
-                self.reducer.launch_flat(rt["flat"].get("seg"))
-                st["seg_launched"] = True
-            if st["mean"] is not None and self.norm_method == "instance":
-                red = eng.f32(B * 3, 2)
-                L.call("csbsr_instnorm_bwd", _ptr(dxin.t), dxin.ld, _ptr(st["sr32"]), _ptr(st["mean"]), _ptr(st["invstd"]), _ptr(dsr32), 0,
-                       B, 3, hw, _ptr(red), eng.stream)
-            else:
-                eng.fm_to_nchw32(dxin, dsr32, 3)
-                if st["invstd"] is not None:
-                    dsr32 *= st["invstd"].reshape(B, 3, 1, 1)
-            del dxin, dseg32, daux32
-        else:
-            psp.saved = None
-            if self.blur_skip or detector_only:
-                return self._finish_backward(pnames, gs, (), st)
-        dkvec = self._sr_loss_seed(st, dsr_loss, gs, dsr32)
-        # ---- KBPN backward (per micro-batch; recompute the forward when it was not kept)
-        if st["saves"] is None:        # forward_from_sr: the graph ends at the given SR image
-            self.last_dsr, self.last_dkvec = dsr32 / gs, dkvec / gs
-            return self._finish_backward(pnames, gs, ("segmentation_model",) if seg_active else (), st)
-        st["kbpn_launched"] = self._kbpn_backward_schedule(st, dsr32, dkvec)
-        return self._finish_backward(pnames, gs, ("sr_model",), st)
+            det = dict(mask=mask, mean=mean, invstd=invstd, seg32=seg32, aux32=aux32, sdf=sdf, sums_m=sums_m, sums_a=sums_a, alpha=alpha,
+                       psp_saved=psp_saved)
+            st = self._saved_state(iter, x, det, hr, kgt, sr32, kvec, saves, mb, terms)
+            seg_loss, sr_loss = _StepFn.apply(self, st, seg_loss, sr_loss, *self.parameters())
+        return seg_loss, sr_loss, seg32, sr32, torch.zeros_like(kgt) if kpred is None else kpred
 
 
 class SRModelWithLoss(_TrainBase):
@@ -813,34 +764,13 @@ class SRModelWithLoss(_TrainBase):
         self._init_loss_scale()
 
     def forward(self, iter, x, sr_targets=None, kernel_targets=None):
-        rt = self._runtime()
-        kbpn = rt["kbpn"]
-        kbpn.training_mode, kbpn.pad_dropout = self.training, self.dropout_enabled and self.dropout_masks is None
-        self._invalidate()              # master weights may have been stepped by the optimiser
-        x, hr, kgt = self._mount(x), self._mount(sr_targets), self._mount(kernel_targets)
-        B, _, h, w = x.shape
+        x, hr, kgt = self._begin(x, sr_targets, kernel_targets)
         sr32, kvec, saves, mb = self._kbpn_forward(iter, x, kgt)
         sr_loss, kpred, terms = self._sr_loss_terms(iter, x, hr, kgt, sr32, kvec, None, None)
         if self.training and torch.is_grad_enabled():
-            st = dict(iter=iter, x=x, hr=hr, kgt=kgt, sr32=sr32, kvec=kvec, saves=saves, mb=mb, B=B, h=h, w=w, n_res=self._n_res,
-                      pad_takes=self._pad_takes, **terms)
-            sr_loss = _SRFn.apply(self, st, sr_loss, *[p for p in self.parameters()])
+            st = self._saved_state(iter, x, None, hr, kgt, sr32, kvec, saves, mb, terms)
+            sr_loss = _StepFn.apply(self, st, None, sr_loss, *self.parameters())[1]
         return sr_loss, sr32, kpred
-
-    def _hip_backward(self, st, dsr_loss):
-        rt, pc = self._rt, self.pc
-        eng = rt["eng"]
-        B, H, W = st["B"], st["h"] * pc.scale, st["w"] * pc.scale
-        gs = self.grad_scale or float(2 ** (round(math.log2(B * H * W)) - self.scale_backoff))      # the PSPNet rule of the joint model
-        eng.grad_scale = gs
-        pnames = [k for k, v in self._named_full() if isinstance(v, nn.Parameter)]     # == self.parameters() order
-        for k in pnames:                    # fresh fp32 accumulators for this backward
-            rt["P"][k].gacc_touched = False
-        torch._foreach_zero_(list(rt["flat"].values()))
-        dsr32 = eng.f32(B, 3, H, W)
-        dkvec = self._sr_loss_seed(st, dsr_loss, gs, dsr32)
-        st["kbpn_launched"] = self._kbpn_backward_schedule(st, dsr32, dkvec)
-        return self._finish_backward(pnames, gs, ("sr_model",), st)
 
 
 class JointModel(_JointBase):
@@ -852,25 +782,16 @@ class JointModel(_JointBase):
 
     @torch.no_grad()
     def forward(self, x, damy_kernel, sr_targets=None):
-        rt = self._runtime()
-        eng, kbpn, psp = rt["eng"], rt["kbpn"], rt["psp"]
-        if self.bicubic:        # build_model.py:69-73 + clip_sr: the clip is the up-sampler's own
-            self._invalidate()
-            x, kgt = self._mount(x), self._mount(damy_kernel)
-            sr32 = self._bicubic_up(x, clip=True)
-            xin, _, _ = self._norm_sr(sr32)
-            seg32, _ = psp.forward(xin, {k: None for k in psp.drop_keys}, training=self.training)
-            psp.saved = None
-            return sr32, seg32, torch.zeros_like(kgt)
-        kbpn.training_mode = self.training
-        self._invalidate()
-        x, kgt = self._mount(x), self._mount(damy_kernel)
-        B = x.shape[0]
-        sr32, kvec = kbpn.forward(x, -1, kgt, save=False)
-        sr32.clamp_(0, 1)
+        x, kgt = self._begin(x, damy_kernel)
+        kbpn, psp = self._rt["kbpn"], self._rt["psp"]
+        if self._has_kbpn:
+            sr32, kvec = kbpn.forward(x, -1, kgt, save=False)
+            sr32.clamp_(0, 1)
+        else:                   # build_model.py:69-73 + clip_sr: the clip is the up-sampler's own
+            sr32, kvec = self._bicubic_up(x, clip=True), None
         xin, _, _ = self._norm_sr(sr32)
-        seg32, _ = psp.forward(xin, {k: None for k in psp.drop_keys}, training=self.training,
-                               kvec=kvec if self.blur_skip else None)
+        seg32, _ = psp.forward(xin, {k: None for k in psp.drop_keys}, training=self.training, kvec=kvec if self.blur_skip else None)
         psp.saved = None
-        kvec = kvec / kvec.sum(1, keepdim=True)
-        return sr32, seg32, kvec.reshape(B, 1, self.ksize, self.ksize)
+        if kvec is None:
+            return sr32, seg32, torch.zeros_like(kgt)
+        return sr32, seg32, (kvec / kvec.sum(1, keepdim=True)).reshape(x.shape[0], 1, self.ksize, self.ksize)

@@ -37,6 +37,7 @@ writes the file every ``MODEL.SR_SCRATCH = False`` model starts from.
 Out of scope: the first-batch PNG dumps of trainer.py:186-227 and :355-386, data-parallel SR pretraining (``do_pretrain_sr`` refuses it), and
 every cfg value the model constructors refuse (they keep raising there).
 """
+import collections
 import datetime
 import os
 import time
@@ -200,12 +201,17 @@ class ValidationAccumulator:
     sums and the image count; ``result`` makes ONE SUM all-reduce of that table and aggregates as above over the GLOBAL batches:
     per-batch loss = sum / count, then the mean over batches; metrics are sums / images.  Every rank gets the same numbers, those of a
     one-rank pass over the same global batches (up to the rounding of the per-batch means, fp64 here where a one-rank pass takes an fp32
-    mean).  Every rank must add the same number of batches.  ``device``: where the table lives when the rank saw nothing but empty slices."""
+    mean).  Every rank must add the same number of batches.  ``device``: where the table lives when the rank saw nothing but empty slices.
 
+    ``losses`` / ``metrics`` name what a single-rank pass of another regime carries (``validate_sr``: one loss, three metrics, fed through
+    ``add_rows``); the rule and the one read-back are the same."""
+
+    LOSSES = ("eval_segment_loss", "eval_sr_loss")
     METRICS = ("psnr", "ssim", "kernel_psnr", "iou")
 
-    def __init__(self, process_group=None, device=None):
-        self.losses, self.metrics = [], {k: [] for k in self.METRICS}
+    def __init__(self, process_group=None, device=None, losses=LOSSES, metrics=METRICS):
+        self.loss_keys, self.metric_keys = tuple(losses), tuple(metrics)
+        self.losses, self.metrics = [], {k: [] for k in self.metric_keys}
         self.pg, self.device = process_group, device
         self.rows, self.totals = [], None          # with a process group: fp64 [3] per global batch (None: a zero row), fp64 [5] metric sums + images
 
@@ -226,8 +232,13 @@ class ValidationAccumulator:
             tot = torch.stack([m.sum() for m in ms] + [seg.new_tensor(float(ms[0].numel()))])
             self.totals = tot if self.totals is None else self.totals + tot
             return
-        self.losses.append(torch.stack([torch.as_tensor(segment_loss).float().mean(), torch.as_tensor(sr_loss).float().mean()]))
-        for k, v in zip(self.METRICS, (psnr, ssim, kernel_psnr, iou)):
+        self.add_rows((segment_loss, sr_loss), (psnr, ssim, kernel_psnr, iou))
+
+    def add_rows(self, losses, metrics):
+        """one batch of a single-rank pass: its per-sample loss vectors in the order of ``losses``, its per-sample metric vectors in the
+        order of ``metrics``"""
+        self.losses.append(torch.stack([torch.as_tensor(v).float().mean() for v in losses]))
+        for k, v in zip(self.metric_keys, metrics):
             self.metrics[k].append(torch.as_tensor(v).float().reshape(-1))
 
     def _result_reduced(self):
@@ -253,15 +264,34 @@ class ValidationAccumulator:
             return self._result_reduced()
         if not self.losses:
             raise ValueError("validation saw no batch")
-        nb = len(self.losses)
-        n = int(sum(v.numel() for v in self.metrics["psnr"]))
-        flat = torch.cat([torch.stack(self.losses).reshape(-1)] + [torch.cat(self.metrics[k]) for k in self.METRICS]).cpu().double().tolist()
-        losses, rest = flat[:2 * nb], flat[2 * nb:]
-        out = {"eval_segment_loss": sum(losses[0::2]) / nb, "eval_sr_loss": sum(losses[1::2]) / nb}
-        for i, k in enumerate(self.METRICS):
+        nb, nl = len(self.losses), len(self.loss_keys)
+        n = int(sum(v.numel() for v in self.metrics[self.metric_keys[0]]))
+        flat = torch.cat([torch.stack(self.losses).reshape(-1)] + [torch.cat(self.metrics[k]) for k in self.metric_keys]).cpu().double().tolist()
+        losses, rest = flat[:nl * nb], flat[nl * nb:]
+        out = {k: sum(losses[i::nl]) / nb for i, k in enumerate(self.loss_keys)}
+        for i, k in enumerate(self.metric_keys):
             out[k] = sum(rest[i * n:(i + 1) * n]) / n
         out["batches"], out["images"] = nb, n
         return out
+
+
+def _validation_pass(model, loader, seed, acc, add_batch):
+    """The skeleton ``validate`` and ``validate_sr`` share: re-seed the loader's generator (``seed`` not None), the model in ``eval()`` under
+    ``no_grad``, ``add_batch(batch)`` for every batch the rank holds rows of, the mode restored, ``acc.result()``."""
+    if seed is not None:
+        loader.gen.manual_seed(int(seed))
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for batch in loader:
+                if batch is None:
+                    acc.add_empty()
+                else:
+                    add_batch(batch)
+    finally:
+        model.train(was_training)
+    return acc.result()
 
 
 def validate(model, loader, iteration, *, seed=None, process_group=None):
@@ -277,28 +307,18 @@ def validate(model, loader, iteration, *, seed=None, process_group=None):
     ``DeviceTrainLoader(shuffle=False, shard=(rank, world), shard_mode="batch")``, every rank walks the same global batches (a None
     batch is one of which the rank holds nothing: no forward) and gets the result over all of them (ValidationAccumulator)."""
     from .utils.estimate_metrics import iou_sweep, psnr_ssim
-    if seed is not None:
-        loader.gen.manual_seed(int(seed))
-    was_training = model.training
     pg = _dist(process_group)[0]
     acc = ValidationAccumulator() if pg is None else ValidationAccumulator(pg, _device_of(model))
-    model.eval()
-    try:
-        with torch.no_grad():
-            for batch in loader:
-                if batch is None:
-                    acc.add_empty()
-                    continue
-                x, hr, mask, k = batch[:4]
-                extra = {"segment_sdf": batch[4]} if len(batch) > 4 else {}
-                seg_l, sr_l, seg, sr, kp = model(iteration, x, sr_targets=hr, segment_targets=mask, kernel_targets=k, **extra)
-                ps, ss = psnr_ssim(sr.clamp(0, 1), hr)
-                kps, _ = psnr_ssim(kp.clamp(0, 1), k)
-                iou = iou_sweep((seg >= 0.5).float(), mask, [0.5])
-                acc.add(seg_l, sr_l, ps, ss, kps, iou)
-    finally:
-        model.train(was_training)
-    return acc.result()
+
+    def add_batch(batch):
+        x, hr, mask, k = batch[:4]
+        extra = {"segment_sdf": batch[4]} if len(batch) > 4 else {}
+        seg_l, sr_l, seg, sr, kp = model(iteration, x, sr_targets=hr, segment_targets=mask, kernel_targets=k, **extra)
+        ps, ss = psnr_ssim(sr.clamp(0, 1), hr)
+        kps, _ = psnr_ssim(kp.clamp(0, 1), k)
+        iou = iou_sweep((seg >= 0.5).float(), mask, [0.5])
+        acc.add(seg_l, sr_l, ps, ss, kps, iou)
+    return _validation_pass(model, loader, seed, acc, add_batch)
 
 
 # ------------------------------------------------------------------------------------------------------------------ checkpoints
@@ -420,6 +440,73 @@ def resume(cfg, output_dir, iteration, model, optimizer, train_loader, process_g
 
 
 # ------------------------------------------------------------------------------------------------------------------ the loop
+# What differs between the training regimes, for ``_loop``: ``names`` (the constant fields of every record), ``n_sums`` (how many batch means
+# the window sums carry), ``begin(iteration)`` (called first in an iteration, before ``model.train()``; may be None), ``losses(iteration,
+# batch) -> (the scalar to back-propagate, its n_sums batch means)``, ``record(window means) -> the loss fields of a log record`` and
+# ``evaluate(iteration) -> a validation result``.
+_Regime = collections.namedtuple("_Regime", "names n_sums begin losses record evaluate")
+
+
+def _loop(regime, model, optimizer, scheduler, train_loader, eval_loader, resume_iter, log_step, save_step, eval_step, output_dir, log, hooks,
+          process_group=None, pg=None, world=1):
+    """The loop of ``do_train`` and ``do_pretrain_sr``: hooks, the step, the fp64 window sums on the device and their single read-back per
+    ``log_step``, the overflow count, timing and ETA, and the checkpoint / eval / log cadence.  ``pg`` / ``world``: the data-parallel group
+    (None: single process) the window sums are averaged over."""
+    before, after = _hook(hooks, "before_step"), _hook(hooks, "after_step")
+    sums, overflowed = None, 0
+    carried = model.__dict__.pop("_resume_logging", None)
+    if carried is not None and carried[0] == resume_iter:
+        sums, overflowed = carried[1]["sums"].to(torch.float64), int(carried[1]["overflowed"])
+    try:
+        max_iter = len(train_loader) + resume_iter - int(getattr(train_loader, "produced", 0))
+    except TypeError:
+        max_iter = None
+    trained_time, tic, end = 0.0, time.time(), time.time()
+    for iteration, batch in enumerate(train_loader, resume_iter + 1):
+        if before is not None:
+            before(iteration, model)
+        if regime.begin is not None:
+            regime.begin(iteration)
+        model.train()
+        optimizer.zero_grad()
+        loss, means = regime.losses(iteration, batch)
+        loss.backward()
+        optimizer.step()
+        scheduler.step()
+        step_sums = torch.stack([v.detach() for v in means]).double()
+        sums = step_sums if sums is None else sums.to(step_sums.device) + step_sums
+        overflowed += bool(getattr(model, "last_step_overflowed", False))
+        del loss, means, batch
+        trained_time += time.time() - end
+        end = time.time()
+
+        record = None
+        if iteration % log_step == 0:
+            if pg is not None:          # equal shards: the mean over the ranks is the mean over the global batch
+                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=pg)
+                sums = sums / world
+            window = [v / log_step for v in sums.tolist()]          # the one read-back of the window
+            eta = "?" if max_iter is None else str(datetime.timedelta(seconds=int(trained_time / (iteration - resume_iter)
+                                                                                  * (max_iter - iteration))))
+            record = {"iteration": iteration, "lr": optimizer.param_groups[0]["lr"], **regime.record(window),
+                      "overflow_steps": overflowed, "cost_s": time.time() - tic, "eta": eta, **regime.names}
+            log(record)
+            sums = None
+            tic = time.time()
+
+        if output_dir is not None and iteration % save_step == 0:
+            paths = save_checkpoint(output_dir, iteration, model, optimizer, train_loader,
+                                    torch.zeros(regime.n_sums, dtype=torch.float64, device=_device_of(model)) if sums is None else sums,
+                                    overflowed, process_group=process_group)
+            log({"iteration": iteration, "checkpoint": paths["model"], **paths})
+
+        if eval_loader is not None and iteration % eval_step == 0:
+            log({"iteration": iteration, **regime.evaluate(iteration), **regime.names})
+
+        if after is not None:
+            after(iteration, model, record)
+
+
 def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *, resume_iter=0, log_step=50, save_step=2000, eval_step=2000,
              output_dir=None, log=print_line, hooks=None, process_group=None):
     """Train over ``train_loader`` (any iterable of ``(x, hr, mask, k)`` or ``(x, hr, mask, k, sdf)``), iterations counted from
@@ -452,70 +539,31 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
         agree.assert_replicas_agree(replica_tensors(model), pg, what="parameters and buffers after the broadcast")
         if rank != 0:
             log = lambda record: None          # noqa: E731  (rank 0 speaks for the run)
-    before, after = _hook(hooks, "before_step"), _hook(hooks, "after_step")
-    names = {"seg_loss_func": cfg.SOLVER.SEG_LOSS_FUNC, "sr_loss_func": cfg.SOLVER.SR_LOSS_FUNC}
-    sums, overflowed = None, 0
-    carried = model.__dict__.pop("_resume_logging", None)
-    if carried is not None and carried[0] == resume_iter:
-        sums, overflowed = carried[1]["sums"].to(torch.float64), int(carried[1]["overflowed"])
-    try:
-        max_iter = len(train_loader) + resume_iter - int(getattr(train_loader, "produced", 0))
-    except TypeError:
-        max_iter = None
-    trained_time, tic, end = 0.0, time.time(), time.time()
-    for iteration, batch in enumerate(train_loader, resume_iter + 1):
-        if before is not None:
-            before(iteration, model)
-        set_alpha_phase(cfg, model, iteration)
-        model.train()
-        optimizer.zero_grad()
+
+    def losses(iteration, batch):
         x, hr, mask, k = batch[:4]
         extra = {"segment_sdf": batch[4]} if len(batch) > 4 else {}
         segment_loss, sr_loss = model(iteration, x, sr_targets=hr, segment_targets=mask, kernel_targets=k, **extra)[:2]
         # (no SR loss -- MODEL.SR == "bicubic" -- : its window sum stays 0 and the scalar is the segmentation mean, see calc_loss)
         seg, sr = segment_loss.mean(), (segment_loss.new_zeros(()) if sr_loss is None else sr_loss.mean())
-        loss = _scalar(seg, sr, iteration, cfg)
-        loss.backward()
-        optimizer.step()
-        scheduler.step()
-        step_sums = torch.stack([seg.detach(), sr.detach()]).double()
-        sums = step_sums if sums is None else sums.to(step_sums.device) + step_sums
-        overflowed += bool(getattr(model, "last_step_overflowed", False))
-        del loss, segment_loss, sr_loss, seg, sr, batch, x, hr, mask, k, extra
-        trained_time += time.time() - end
-        end = time.time()
+        return _scalar(seg, sr, iteration, cfg), (seg, sr)
 
-        record = None
-        if iteration % log_step == 0:
-            if pg is not None:          # equal shards: the mean over the ranks is the mean over the global batch
-                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=pg)
-                sums = sums / world
-            seg_m, sr_m = (v / log_step for v in sums.tolist())          # the one read-back of the window
-            eta = "?" if max_iter is None else str(datetime.timedelta(seconds=int(trained_time / (iteration - resume_iter)
-                                                                                  * (max_iter - iteration))))
-            fn = getattr(model, "ss_loss_fn", None)
-            record = {"iteration": iteration, "lr": optimizer.param_groups[0]["lr"], "segment_loss": seg_m, "sr_loss": sr_m,
-                      "total": sr_m + cfg.SOLVER.TASK_LOSS_WEIGHT * seg_m,
-                      "boundary_alpha": fn.alpha if fn is not None and "Boundary" in cfg.SOLVER.SEG_LOSS_FUNC else None,
-                      "overflow_steps": overflowed, "cost_s": time.time() - tic, "eta": eta, **names}
-            log(record)
-            sums = None
-            tic = time.time()
+    def record(window):
+        seg_m, sr_m = window
+        fn = getattr(model, "ss_loss_fn", None)
+        return {"segment_loss": seg_m, "sr_loss": sr_m, "total": sr_m + cfg.SOLVER.TASK_LOSS_WEIGHT * seg_m,
+                "boundary_alpha": fn.alpha if fn is not None and "Boundary" in cfg.SOLVER.SEG_LOSS_FUNC else None}
 
-        if output_dir is not None and iteration % save_step == 0:
-            paths = save_checkpoint(output_dir, iteration, model, optimizer, train_loader, sums, overflowed, process_group=process_group)
-            log({"iteration": iteration, "checkpoint": paths["model"], **paths})
-
-        if eval_loader is not None and iteration % eval_step == 0:
-            model.iter_cnt = False
-            try:
-                result = validate(model, eval_loader, iteration, process_group=process_group)
-            finally:
-                model.iter_cnt = True
-            log({"iteration": iteration, **result, **names})
-
-        if after is not None:
-            after(iteration, model, record)
+    def evaluate(iteration):
+        model.iter_cnt = False
+        try:
+            return validate(model, eval_loader, iteration, process_group=process_group)
+        finally:
+            model.iter_cnt = True
+    regime = _Regime({"seg_loss_func": cfg.SOLVER.SEG_LOSS_FUNC, "sr_loss_func": cfg.SOLVER.SR_LOSS_FUNC}, 2,
+                     lambda iteration: set_alpha_phase(cfg, model, iteration), losses, record, evaluate)
+    _loop(regime, model, optimizer, scheduler, train_loader, eval_loader, resume_iter, log_step, save_step, eval_step, output_dir, log, hooks,
+          process_group, pg, world)
 
 
 # ------------------------------------------------------------------------------------------------------------------ SR-only pretraining
@@ -537,31 +585,15 @@ def validate_sr(model, loader, iteration, *, seed=None):
     the SR loss averaged over BATCHES, PSNR, SSIM and kernel PSNR averaged over IMAGES with the SR image and the kernel clamped to [0, 1].
     ``seed`` as in ``validate``; the model's mode is restored."""
     from .utils.estimate_metrics import psnr_ssim
-    if seed is not None:
-        loader.gen.manual_seed(int(seed))
-    was_training = model.training
-    losses, metrics = [], {"psnr": [], "ssim": [], "kernel_psnr": []}
-    model.eval()
-    try:
-        with torch.no_grad():
-            for x, hr, k in loader:
-                sr_l, sr, kp = model(iteration, x, sr_targets=hr, kernel_targets=k)
-                ps, ss = psnr_ssim(sr.clamp(0, 1), hr)
-                kps, _ = psnr_ssim(kp.clamp(0, 1), k)
-                losses.append(torch.as_tensor(sr_l).float().mean())
-                for key, v in zip(metrics, (ps, ss, kps)):
-                    metrics[key].append(torch.as_tensor(v).float().reshape(-1))
-    finally:
-        model.train(was_training)
-    if not losses:
-        raise ValueError("validation saw no batch")
-    nb, n = len(losses), int(sum(v.numel() for v in metrics["psnr"]))
-    flat = torch.cat([torch.stack(losses)] + [torch.cat(metrics[key]) for key in metrics]).cpu().double().tolist()      # the one read-back
-    out = {"eval_sr_loss": sum(flat[:nb]) / nb}
-    for i, key in enumerate(metrics):
-        out[key] = sum(flat[nb + i * n:nb + (i + 1) * n]) / n
-    out["batches"], out["images"] = nb, n
-    return out
+    acc = ValidationAccumulator(losses=("eval_sr_loss",), metrics=("psnr", "ssim", "kernel_psnr"))
+
+    def add_batch(batch):
+        x, hr, k = batch
+        sr_l, sr, kp = model(iteration, x, sr_targets=hr, kernel_targets=k)
+        ps, ss = psnr_ssim(sr.clamp(0, 1), hr)
+        kps, _ = psnr_ssim(kp.clamp(0, 1), k)
+        acc.add_rows((sr_l,), (ps, ss, kps))
+    return _validation_pass(model, loader, seed, acc, add_batch)
 
 
 def export_pretrained_sr(model_or_state_dict, cfg, root="weights"):
@@ -590,51 +622,10 @@ def do_pretrain_sr(cfg, model, optimizer, scheduler, train_loader, eval_loader=N
     and its result goes to ``log``.  Data-parallel pretraining is not built: NotImplementedError before anything touches the device."""
     if _forced() or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
         raise NotImplementedError("do_pretrain_sr is single-GPU: data-parallel SR pretraining is not built")
-    before, after = _hook(hooks, "before_step"), _hook(hooks, "after_step")
-    names = {"sr_loss_func": cfg.SOLVER.SR_LOSS_FUNC}
-    sums, overflowed = None, 0
-    carried = model.__dict__.pop("_resume_logging", None)
-    if carried is not None and carried[0] == resume_iter:
-        sums, overflowed = carried[1]["sums"].to(torch.float64), int(carried[1]["overflowed"])
-    try:
-        max_iter = len(train_loader) + resume_iter - int(getattr(train_loader, "produced", 0))
-    except TypeError:
-        max_iter = None
-    trained_time, tic, end = 0.0, time.time(), time.time()
-    for iteration, (x, hr, k) in enumerate(train_loader, resume_iter + 1):
-        if before is not None:
-            before(iteration, model)
-        model.train()
-        optimizer.zero_grad()
-        sr_loss = model(iteration, x, sr_targets=hr, kernel_targets=k.detach())[0].mean()
-        sr_loss.backward()
-        optimizer.step()
-        scheduler.step()
-        step_sums = sr_loss.detach().double().reshape(1)
-        sums = step_sums if sums is None else sums.to(step_sums.device) + step_sums
-        overflowed += bool(getattr(model, "last_step_overflowed", False))
-        del sr_loss, x, hr, k
-        trained_time += time.time() - end
-        end = time.time()
-
-        record = None
-        if iteration % log_step == 0:
-            sr_m = sums.tolist()[0] / log_step          # the one read-back of the window
-            eta = "?" if max_iter is None else str(datetime.timedelta(seconds=int(trained_time / (iteration - resume_iter)
-                                                                                  * (max_iter - iteration))))
-            record = {"iteration": iteration, "lr": optimizer.param_groups[0]["lr"], "sr_loss": sr_m, "overflow_steps": overflowed,
-                      "cost_s": time.time() - tic, "eta": eta, **names}
-            log(record)
-            sums = None
-            tic = time.time()
-
-        if output_dir is not None and iteration % save_step == 0:
-            paths = save_checkpoint(output_dir, iteration, model, optimizer, train_loader,
-                                    torch.zeros(1, dtype=torch.float64) if sums is None else sums, overflowed)
-            log({"iteration": iteration, "checkpoint": paths["model"], **paths})
-
-        if eval_loader is not None and iteration % eval_step == 0:
-            log({"iteration": iteration, **validate_sr(model, eval_loader, iteration), **names})
-
-        if after is not None:
-            after(iteration, model, record)
+    def losses(iteration, batch):
+        x, hr, k = batch
+        sr = model(iteration, x, sr_targets=hr, kernel_targets=k.detach())[0].mean()
+        return sr, (sr,)
+    regime = _Regime({"sr_loss_func": cfg.SOLVER.SR_LOSS_FUNC}, 1, None, losses, lambda window: {"sr_loss": window[0]},
+                     lambda iteration: validate_sr(model, eval_loader, iteration))
+    _loop(regime, model, optimizer, scheduler, train_loader, eval_loader, resume_iter, log_step, save_step, eval_step, output_dir, log, hooks)
