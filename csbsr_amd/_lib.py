@@ -220,7 +220,7 @@ ENV_HOOKS = (
     # up_conv3's epilogue-backward pass on kb.sr_reconst's dgrad (csrc/conv_thin.hip, DACT): 26 GB per step less fabric traffic, but the
     # fused launch is no faster than the two it replaces (1065 vs 1067 ms per step, same run) -- opt-in
     Hook("CSBSR_THIN_DACT", "0", "thin_dact", _is1),
-    Hook("CSBSR_FOLD_PRELU", "1", "fold_prelu", _is1),           # pspnet.py _blur_skip_bwd (A/B timing: 0)
+    Hook("CSBSR_FOLD_PRELU", "1", "fold_prelu", _is1),           # blocks.py sft_bwd, BlurSkip's learned slopes (A/B timing: 0)
     # Weight gradients on a second HIP stream (opt-in, CSBSR_WGRAD_STREAM=1).  In the backward a layer's wgrad is a side branch (it
     # only feeds the parameter's gradient accumulator) while the dgrad chain is the critical path; the wgrads are MFMA-bound on
     # L2-resident tiles, much of what the chain runs between two of its convolutions is HBM-bound, so two streams could let the

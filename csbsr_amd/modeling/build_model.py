@@ -515,7 +515,11 @@ class _TrainBase(_JointBase):
         # unused output): a function of the training phase, identical on every rank, and no device read-back
         seg_active = self._has_detector and dseg_loss is not None
         if self._has_detector:
-            psp.saved = st["psp_saved"] if seg_active else None
+            # the node's reference ends here: the detector's backward consumes the tape entry by entry, and an iteration without a
+            # segmentation loss (SR pretraining phase) frees all of it before the KBPN backward
+            tape = st.pop("psp_saved")
+            psp.saved = tape if seg_active else None
+            del tape
         if seg_active:
             gsc = (dseg_loss.to(torch.float32) * gs).contiguous()
             dseg32, daux32 = eng.f32(B, 1, H, W, zero=False), eng.f32(B, 1, H, W, zero=False)
@@ -715,7 +719,9 @@ class JointModelWithLoss(_TrainBase):
         drop = {k: (None if v is None else v.to(self._device, torch.float32).contiguous()) for k, v in drop.items()}
         seg32, aux32 = psp.forward(xin, drop, training, kvec=kvec if self.blur_skip else None)
         keep = training and torch.is_grad_enabled()
-        psp_saved, psp.saved = (psp.saved if keep else None), None      # carried by the autograd node, not by the (shared) layer object
+        # the detector's tape (None unless ``keep``: the forward writes none otherwise) is carried by the autograd node, not by the (shared)
+        # detector object: nothing a backward reads stays on a layer
+        psp_saved, psp.saved = psp.saved, None
         # ---- losses (forward sums only; gradients are produced in _hip_backward)
         hw = H * W
         if sdf is None:
@@ -791,7 +797,6 @@ class JointModel(_JointBase):
             sr32, kvec = self._bicubic_up(x, clip=True), None
         xin, _, _ = self._norm_sr(sr32)
         seg32, _ = psp.forward(xin, {k: None for k in psp.drop_keys}, training=self.training, kvec=kvec if self.blur_skip else None)
-        psp.saved = None
         if kvec is None:
             return sr32, seg32, torch.zeros_like(kgt)
         return sr32, seg32, (kvec / kvec.sum(1, keepdim=True)).reshape(x.shape[0], 1, self.ksize, self.ksize)

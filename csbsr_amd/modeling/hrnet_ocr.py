@@ -18,84 +18,53 @@ import torch
 import torch.nn.functional as F
 
 from .. import _lib as L
-from ..engine import FM, Conv, BatchNorm, grad_acc, pad8, _ptr
-from .pspnet import ConvBN
+from ..engine import FM, Conv, grad_acc, _ptr
+from .blocks import ConvBN, act_bwd
 from .shapes import HRNET_W48
 
 DROP_P = {"ocr_drop": 0.05}        # spatial_ocr_block.py:283 / nets/hrnet.py:125
 DROP_C = {"ocr_drop": 512}
 
 
-class CBN:
-    """conv (+bias) -> train-mode BatchNorm -> optional residual add -> optional ReLU, with its backward."""
-
-    def __init__(self, eng, P, conv, norm, k, stride=1, bias=False, relu=True):
-        self.u = ConvBN(eng, P, conv, norm, None, P[conv + ".weight"].shape[0], k, stride, (k - 1) // 2, bias=bias)
-        self.eng, self.act = eng, L.ACT_RELU if relu else L.ACT_NONE
-        self.sv = None
-
-    @property
-    def conv(self):
-        return self.u.conv
-
-    def fwd(self, x, training, res=None, out=None, drop=None, keep=True):
-        raw, m, iv = self.u.fwd(x, training)
-        y = self.u.bn.apply(raw, m, iv, act=self.act, res=res, drop=drop, out=out)
-        self.sv = (x, raw, m, iv, res, drop) if keep else None
-        return y
-
-    def bwd(self, dy, dres=None, dres_acc=False, dx_out=None, dx_acc=False, need_dx=True):
-        x, raw, m, iv, res, drop = self.sv
-        self.sv = None
-        draw = self.u.bn.backward(dy, raw, m, iv, act=self.act, res=res, drop=drop, dres=dres, dres_acc=dres_acc)
-        self.conv.bwd_weights(draw, x)
-        if self.conv.b is not None:
-            grad_acc(self.conv.b)          # bias feeding train-mode BN: identically zero gradient (not None)
-        if not need_dx:
-            return None
-        xs = x if isinstance(x, (tuple, list)) else (x,)
-        return self.conv.bwd_input(draw, out=dx_out, accumulate=dx_acc, in_hw=(xs[0].H, xs[0].W))
-
-
 class _Basic:
     def __init__(self, eng, P, pre):
-        self.c1 = CBN(eng, P, pre + ".conv1", pre + ".bn1", 3)
-        self.c2 = CBN(eng, P, pre + ".conv2", pre + ".bn2", 3)
+        self.c1 = ConvBN(eng, P, pre + ".conv1", pre + ".bn1", 3)
+        self.c2 = ConvBN(eng, P, pre + ".conv2", pre + ".bn2", 3)
         self.eng = eng
 
     def cbns(self):
         return [self.c1, self.c2]
 
-    def fwd(self, x, training):
-        return self.c2.fwd(self.c1.fwd(x, training), training, res=x)
+    def fwd(self, x, training, tape):
+        return self.c2.fwd(self.c1.fwd(x, training, tape), training, tape, res=x)
 
-    def bwd(self, dy):
+    def bwd(self, tape, dy):
         dx = self.eng.new(dy.N, dy.H, dy.W, dy.c)
-        da = self.c2.bwd(dy, dres=dx)
-        self.c1.bwd(da, dx_out=dx, dx_acc=True)
+        da = self.c2.bwd(tape, dy, dres=dx)
+        self.c1.bwd(tape, da, dx_out=dx, dx_acc=True)
         return dx
 
 
 class _Bottleneck:
     def __init__(self, eng, P, pre, has_down):
-        self.c1 = CBN(eng, P, pre + ".conv1", pre + ".bn1", 1)
-        self.c2 = CBN(eng, P, pre + ".conv2", pre + ".bn2", 3)
-        self.c3 = CBN(eng, P, pre + ".conv3", pre + ".bn3", 1)
-        self.down = CBN(eng, P, pre + ".downsample.0", pre + ".downsample.1", 1, relu=False) if has_down else None
+        self.c1 = ConvBN(eng, P, pre + ".conv1", pre + ".bn1", 1)
+        self.c2 = ConvBN(eng, P, pre + ".conv2", pre + ".bn2", 3)
+        self.c3 = ConvBN(eng, P, pre + ".conv3", pre + ".bn3", 1)
+        self.down = ConvBN(eng, P, pre + ".downsample.0", pre + ".downsample.1", 1, act=L.ACT_NONE) if has_down else None
         self.eng = eng
 
     def cbns(self):
         return [self.c1, self.c2, self.c3] + ([self.down] if self.down else [])
 
-    def fwd(self, x, training):
-        res = self.down.fwd(x, training) if self.down else x
-        return self.c3.fwd(self.c2.fwd(self.c1.fwd(x, training), training), training, res=res)
+    def fwd(self, x, training, tape):
+        res = self.down.fwd(x, training, tape) if self.down else x
+        return self.c3.fwd(self.c2.fwd(self.c1.fwd(x, training, tape), training, tape), training, tape, res=res)
 
-    def bwd(self, dy):
+    def bwd(self, tape, dy):
         dres = self.eng.new(dy.N, dy.H, dy.W, dy.c)
-        d1 = self.c2.bwd(self.c3.bwd(dy, dres=dres))
-        dx = self.down.bwd(dres) if self.down else dres
-        self.c1.bwd(d1, dx_out=dx, dx_acc=True)
+        d1 = self.c2.bwd(tape, self.c3.bwd(tape, dy, dres=dres))
+        dx = self.down.bwd(tape, dres) if self.down else dres
+        self.c1.bwd(tape, d1, dx_out=dx, dx_acc=True)
         return dx
 
 
@@ -110,10 +79,10 @@ class _HRModule:
             for j in range(self.nb):
                 fp = f"{pre}.fuse_layers.{i}.{j}"
                 if j > i:
-                    self.fuse[i, j] = [CBN(eng, P, fp + ".0", fp + ".1", 1, relu=False)]
+                    self.fuse[i, j] = [ConvBN(eng, P, fp + ".0", fp + ".1", 1, act=L.ACT_NONE)]
                 elif j < i:
-                    self.fuse[i, j] = [CBN(eng, P, f"{fp}.{k}.0", f"{fp}.{k}.1", 3, stride=2, relu=k != i - j - 1) for k in range(i - j)]
-        self.sv = None
+                    self.fuse[i, j] = [ConvBN(eng, P, f"{fp}.{k}.0", f"{fp}.{k}.1", 3, stride=2, act=L.ACT_RELU if k != i - j - 1 else L.ACT_NONE)
+                                       for k in range(i - j)]
 
     def cbns(self):
         out = [c for br in self.branches for blk in br for c in blk.cbns()]
@@ -121,12 +90,12 @@ class _HRModule:
             out += v
         return out
 
-    def fwd(self, xs, training, outs=None):
+    def fwd(self, xs, training, tape, outs=None):
         e = self.eng
         xs = list(xs)
         for i in range(self.nb):
             for blk in self.branches[i]:
-                xs[i] = blk.fwd(xs[i], training)
+                xs[i] = blk.fwd(xs[i], training, tape)
         ys = []
         for i in range(self.nb):
             terms = []
@@ -134,25 +103,26 @@ class _HRModule:
                 if j == i:
                     terms.append(xs[j])
                 elif j > i:
-                    t = self.fuse[i, j][0].fwd(xs[j], training)
+                    t = self.fuse[i, j][0].fwd(xs[j], training, tape)
                     terms.append(e.bilinear(t, xs[i].H, xs[i].W, True))
                 else:
                     t = xs[j]
                     for c in self.fuse[i, j]:
-                        t = c.fwd(t, training)
+                        t = c.fwd(t, training, tape)
                     terms.append(t)
             ys.append(sum_act(e, terms, relu=True, out=None if outs is None else outs[i]))
-        self.sv = (ys, [(x.H, x.W, x.c) for x in xs])
+        if tape is not None:
+            tape[self] = (ys, [(x.H, x.W, x.c) for x in xs])
         return ys
 
-    def bwd(self, dys):
+    def bwd(self, tape, dys):
         """dys[i]: gradient wrt output i (consumed: the ReLU mask is applied in place)."""
         e = self.eng
-        ys, shp = self.sv
-        self.sv = None
+        ys, shp = tape.pop(self)
         dxs = [None] * self.nb
         for i in range(self.nb):
             e.epilogue_bwd(dys[i], out=ys[i], act=L.ACT_RELU, dpre=dys[i])
+        del ys
         for i in range(self.nb):                 # identity terms first: they create the accumulators
             dxs[i] = e.new(dys[i].N, dys[i].H, dys[i].W, dys[i].c)
             L.call("csbsr_axpby", dys[i].npix, dys[i].cp, _ptr(dys[i].t), dys[i].ld, 1.0, None, 0, 0.0, _ptr(dxs[i].t), dxs[i].ld, e.stream)
@@ -162,16 +132,16 @@ class _HRModule:
                     H, W, c = shp[j]
                     dt = e.new(dys[i].N, H, W, dys[i].c)
                     e.bilinear_bwd(dys[i], dt, False, True)
-                    self.fuse[i, j][0].bwd(dt, dx_out=dxs[j], dx_acc=True)
+                    self.fuse[i, j][0].bwd(tape, dt, dx_out=dxs[j], dx_acc=True)
                 elif j < i:
                     d = dys[i]
                     chain = self.fuse[i, j]
                     for k in range(len(chain) - 1, -1, -1):
-                        d = chain[k].bwd(d, dx_out=dxs[j] if k == 0 else None, dx_acc=k == 0)
+                        d = chain[k].bwd(tape, d, dx_out=dxs[j] if k == 0 else None, dx_acc=k == 0)
         for i in range(self.nb - 1, -1, -1):
             d = dxs[i]
             for blk in reversed(self.branches[i]):
-                d = blk.bwd(d)
+                d = blk.bwd(tape, d)
             dxs[i] = d
         return dxs
 
@@ -218,7 +188,7 @@ class HRNetOCR:
     def __init__(self, eng, params, prefix="segmentation_model"):
         self.eng, self.P, self.prefix = eng, params, prefix
         e, P, b = eng, params, prefix + ".backbone"
-        self.stem = [CBN(e, P, b + ".conv1", b + ".bn1", 3, stride=2), CBN(e, P, b + ".conv2", b + ".bn2", 3, stride=2)]
+        self.stem = [ConvBN(e, P, b + ".conv1", b + ".bn1", 3, stride=2), ConvBN(e, P, b + ".conv2", b + ".bn2", 3, stride=2)]
         self.layer1 = [_Bottleneck(e, P, f"{b}.layer1.{i}", i == 0) for i in range(4)]
         self.trans, self.stages = [], []
         prev = (256,)
@@ -227,25 +197,24 @@ class HRNetOCR:
             tr = []
             for i, c in enumerate(chans):
                 if i < len(prev):
-                    tr.append(CBN(e, P, f"{tp}.{i}.0", f"{tp}.{i}.1", 3) if prev[i] != c else None)
+                    tr.append(ConvBN(e, P, f"{tp}.{i}.0", f"{tp}.{i}.1", 3) if prev[i] != c else None)
                 else:
-                    tr.append(CBN(e, P, f"{tp}.{i}.0.0", f"{tp}.{i}.0.1", 3, stride=2))
+                    tr.append(ConvBN(e, P, f"{tp}.{i}.0.0", f"{tp}.{i}.0.1", 3, stride=2))
             self.trans.append(tr)
             self.stages.append([_HRModule(e, P, f"{b}.{stage}.{m}", chans) for m in range(nmod)])
             prev = chans
         self.chans = prev
-        self.aux0 = CBN(e, P, prefix + ".aux_head.0", prefix + ".aux_head.1.0", 3, bias=True)
+        self.aux0 = ConvBN(e, P, prefix + ".aux_head.0", prefix + ".aux_head.1.0", 3, bias=True)
         self.aux2 = Conv(e, prefix + ".aux_head.2", P, 1, bias=True)
-        self.conv3 = CBN(e, P, prefix + ".conv3x3.0", prefix + ".conv3x3.1.0", 3, bias=True)
+        self.conv3 = ConvBN(e, P, prefix + ".conv3x3.0", prefix + ".conv3x3.1.0", 3, bias=True)
         ob = prefix + ".ocr_distri_head.object_context_block"
         self.ob = ob
-        self.f_pixel = [CBN(e, P, ob + ".f_pixel.0", ob + ".f_pixel.1.0", 1, bias=True),
-                        CBN(e, P, ob + ".f_pixel.2", ob + ".f_pixel.3.0", 1, bias=True)]
+        self.f_pixel = [ConvBN(e, P, f"{ob}.f_pixel.{i}", f"{ob}.f_pixel.{i + 1}.0", 1, bias=True) for i in (0, 2)]
         cd = prefix + ".ocr_distri_head.conv_bn_dropout"
-        self.fuse = ConvBN(e, P, cd + ".0", cd + ".1.0", 1024, 512, 1, 1, 0, bias=True)
+        self.fuse = ConvBN(e, P, cd + ".0", cd + ".1.0", 1, bias=True)
         self.fuse.conv.split = (512, 512)
         self.cls = Conv(e, prefix + ".cls_head", P, 1, bias=True)
-        self.saved = None
+        self.saved = None       # the tape of the last training forward (None otherwise); the train step moves it to its autograd node
         self.split = False          # detector_precision == "split" (set by the model; the maps carry it: FM.lo)
 
     # ------------------------------------------------------------------ bookkeeping
@@ -258,10 +227,10 @@ class HRNetOCR:
         for st in self.stages:
             for m in st:
                 out += m.cbns()
-        return out + [self.aux0, self.conv3] + self.f_pixel
+        return out + [self.aux0, self.conv3] + self.f_pixel + [self.fuse]
 
     def all_convs(self):
-        return [c.conv for c in self._cbns()] + [self.aux2, self.fuse.conv, self.cls]
+        return [c.conv for c in self._cbns()] + [self.aux2, self.cls]
 
     def invalidate(self):
         for c in self.all_convs():
@@ -296,80 +265,82 @@ class HRNetOCR:
 
     # ------------------------------------------------------------------ forward
     def forward(self, xin, drop, training=True, kvec=None):
-        """xin: FM [B,H,W,8] (normalised SR image).  Returns (seg32, aux32) fp32 [B,1,H,W] probability maps."""
-        cat, ysz = self._backbone_fwd(xin, training)
-        seg32, aux32 = self._head_fwd(cat, drop, training, xin.H, xin.W)
-        self.saved.update(xin=xin, ysz=ysz)
+        """xin: FM [B,H,W,8] (normalised SR image).  Returns (seg32, aux32) fp32 [B,1,H,W] probability maps.  A training forward with
+        gradients enabled leaves its tape (blocks.py: every unit's saves, the head's under "head") in ``self.saved``."""
+        tape = {} if training and torch.is_grad_enabled() else None
+        cat = self._backbone_fwd(xin, training, tape)
+        seg32, aux32 = self._head_fwd(cat, drop, training, xin.H, xin.W, tape)
+        self.saved = tape
         return seg32, aux32
 
-    def _backbone_fwd(self, xin, training):
+    def _backbone_fwd(self, xin, training, tape):
         """HighResolutionNet.forward + the bilinear concat of nets/hrnet.py:143-149 -> 720-channel map at 1/4 resolution."""
         e = self.eng
         B = xin.N
-        x = self.stem[1].fwd(self.stem[0].fwd(xin, training), training)
+        x = self.stem[1].fwd(self.stem[0].fwd(xin, training, tape), training, tape)
         for blk in self.layer1:
-            x = blk.fwd(x, training)
+            x = blk.fwd(x, training, tape)
         ys = [x]
         cat = None
         for si, (tr, mods) in enumerate(zip(self.trans, self.stages)):
             xs = []
             for i, t in enumerate(tr):
                 src = ys[i] if i < len(ys) else ys[-1]
-                xs.append(t.fwd(src, training) if t is not None else src)
+                xs.append(t.fwd(src, training, tape) if t is not None else src)
             for mi, m in enumerate(mods):
                 outs = None
                 if si == len(self.stages) - 1 and mi == len(mods) - 1:      # branch 0 of the last module lands in the 720-ch concat
                     cat = e.new(B, xs[0].H, xs[0].W, sum(self.chans), split=bool(xs[0].lo))
                     outs = [cat.slice(0, self.chans[0])] + [None] * (len(xs) - 1)
-                xs = m.fwd(xs, training, outs)
+                xs = m.fwd(xs, training, tape, outs)
             ys = xs
         h, w = ys[0].H, ys[0].W
         off = self.chans[0]
         for j in range(1, 4):
             e.bilinear(ys[j], h, w, True, out=cat.slice(off, off + self.chans[j]))
             off += self.chans[j]
-        return cat, [(y.H, y.W) for y in ys]
+        if tape is not None:
+            tape["ysz"] = [(y.H, y.W) for y in ys]
+        return cat
 
-    def _head_fwd(self, cat, drop, training, H, W):
+    def _head_fwd(self, cat, drop, training, H, W, tape):
         """aux head, 3x3 reduction, OCR (gather + distribute), class head, bilinear up + sigmoid (nets/hrnet.py:150-158)."""
         e = self.eng
         B, h, w = cat.N, cat.H, cat.W
-        a = self.aux0.fwd(cat, training)
+        a = self.aux0.fwd(cat, training, tape)
         aux_lo = e.f32(B, 1, h, w, zero=False)
         self.aux2.fwd(a, out32=aux_lo)
-        f = self.conv3.fwd(cat, training)
+        f = self.conv3.fwd(cat, training, tape)
         # soft object region + pooled region vector
         probs = torch.softmax(aux_lo.reshape(B, -1), dim=1).contiguous()
         ctx = e.f32(B, 512)
         L.call("csbsr_weighted_pool_fwd_split", _ptr(f.t), f.ld, f.lo, _ptr(probs), _ptr(ctx), B, h * w, 512, e.stream)
-        keep = training and torch.is_grad_enabled()
+        keep = tape is not None
         ctx_leaf = ctx.detach().requires_grad_(keep)
         with torch.enable_grad() if keep else torch.no_grad():
             cvec, leaves = self._vec_chain(ctx_leaf, training, h * w)
         # f_pixel (query transform): dead for one region, evaluated for its running statistics
-        self.f_pixel[1].fwd(self.f_pixel[0].fwd(f, training, keep=False), training, keep=False)
+        self.f_pixel[1].fwd(self.f_pixel[0].fwd(f, training), training)
         ct = torch.zeros(B, 1, 1, 512, dtype=torch.float16, device=e.device)
         ct[:, 0, 0] = cvec.detach().to(torch.float16)
         cfm = FM(ct, 512, bcast=True, H=h, W=w)
+        pre = None
         if f.lo:     # split-fp16 features: the constant context segment of the 1x1 fuse conv is folded into a per-sample fp32 bias
             if training:
                 stat = self.fuse.bn.new_stat()
                 raw = self.fuse.conv.fwd_const_1x1(cvec.detach(), f, stat=stat, stat_mode=L.STAT_BN)
-                m, iv = self.fuse.bn.finalize(stat, raw.npix, update_running=True)
+                pre = (raw,) + self.fuse.bn.finalize(stat, raw.npix)
             else:
-                raw = self.fuse.conv.fwd_const_1x1(cvec.detach(), f)
-                m, iv = self.fuse.bn.rmean, torch.rsqrt(self.fuse.bn.rvar + 1e-5)
-        else:
-            raw, m, iv = self.fuse.fwd((cfm, f), training)
-        o = self.fuse.bn.apply(raw, m, iv, act=L.ACT_RELU, drop=drop["ocr_drop"])
+                pre = self.fuse.conv.fwd_const_1x1(cvec.detach(), f), self.fuse.bn.rmean, torch.rsqrt(self.fuse.bn.rvar + 1e-5)
+        o = self.fuse.fwd((cfm, f), training, tape, drop=drop["ocr_drop"], pre=pre)
         cls_lo = e.f32(B, 1, h, w, zero=False)
         self.cls.fwd(o, out32=cls_lo)
         seg32, aux32 = e.f32(B, 1, H, W, zero=False), e.f32(B, 1, H, W, zero=False)
         for lo, hi in ((cls_lo, seg32), (aux_lo, aux32)):
             L.call("csbsr_bilinear32_fwd", _ptr(lo), _ptr(hi), B, h, w, H, W, 1, e.stream)
             hi.sigmoid_()
-        self.saved = dict(cat=cat, a=a, f=f, probs=probs, ctx=ctx_leaf, cvec=cvec, leaves=leaves, cfm=cfm, fuse=(raw, m, iv), o=o,
-                          drop=drop["ocr_drop"], seg32=seg32, aux32=aux32, hw=(h, w))
+        if keep:
+            tape["head"] = dict(a=a, f=f, probs=probs, ctx=ctx_leaf, cvec=cvec, leaves=leaves, o=o, seg32=seg32, aux32=aux32)
         return seg32, aux32
 
     # ------------------------------------------------------------------ backward
@@ -383,30 +354,22 @@ class HRNetOCR:
         return lo
 
     def _logit_head_bwd(self, conv, dlogit32, x):
-        e = self.eng
-        dpre = e.nchw32_to_fm(dlogit32)
-        e.epilogue_bwd(dpre, dbias=grad_acc(conv.b), creal=1)
+        dpre = act_bwd(conv, self.eng.nchw32_to_fm(dlogit32))
         conv.bwd_weights(dpre, x)
         return conv.bwd_input(dpre)
 
     def backward(self, dseg32, daux32, need_dxin=True):
         """``need_dxin=False`` (the input is no function of a parameter: MODEL.SR="bicubic") skips the first conv's input gradient: None."""
-        sv = self.saved
-        dcat = self._head_bwd(dseg32, daux32)
-        self.saved = None
-        return self._backbone_bwd(dcat, sv["ysz"], need_dxin)
+        tape, self.saved = self.saved, None
+        return self._backbone_bwd(self._head_bwd(dseg32, daux32, tape), tape, need_dxin)
 
-    def _head_bwd(self, dseg32, daux32):
-        e, sv, P = self.eng, self.saved, self.P
-        B = sv["cat"].N
-        h, w = sv["hw"]
-        f, cat = sv["f"], sv["cat"]
+    def _head_bwd(self, dseg32, daux32, tape):
+        e, sv, P = self.eng, tape.pop("head"), self.P
+        f = sv["f"]
+        B, h, w = f.N, f.H, f.W
         # main head
         do = self._logit_head_bwd(self.cls, self._head_dlogit(dseg32, sv["seg32"], h, w), sv["o"])
-        raw, m, iv = sv["fuse"]
-        draw = self.fuse.bn.backward(do, raw, m, iv, act=L.ACT_RELU, drop=sv["drop"])
-        self.fuse.conv.bwd_weights(draw, (sv["cfm"], f))
-        grad_acc(self.fuse.conv.b)
+        draw, _ = self.fuse.bwd_bn(tape, do)
         df = self.fuse.conv.bwd_input(draw, seg=1)
         dcvec = e.f32(B, 512)
         self.fuse.conv.bwd_input(draw, seg=0, stat=dcvec)
@@ -422,7 +385,7 @@ class HRNetOCR:
             if g is not None:
                 acc.add_(g.reshape(acc.shape))
         for c in self.f_pixel:                       # zero gradients (softmax over a single region), as in the reference
-            grad_acc(c.conv.w), grad_acc(c.conv.b), grad_acc(c.u.bn.gamma), grad_acc(c.u.bn.beta)
+            grad_acc(c.conv.w), grad_acc(c.conv.b), grad_acc(c.bn.gamma), grad_acc(c.bn.beta)
         for seq, idx in (("f_object", 0), ("f_object", 2)):
             for suffix in (f"{idx}.weight", f"{idx}.bias", f"{idx + 1}.0.weight", f"{idx + 1}.0.bias"):
                 grad_acc(P[f"{self.ob}.{seq}.{suffix}"])
@@ -431,18 +394,18 @@ class HRNetOCR:
         L.call("csbsr_weighted_pool_bwd", _ptr(f.t), f.ld, _ptr(sv["probs"]), _ptr(dctx), _ptr(df.t), df.ld, _ptr(dprobs), B, h * w, 512, e.stream)
         probs = sv["probs"]
         dlog_gather = probs * (dprobs - (probs * dprobs).sum(1, keepdim=True))
-        dcat = self.conv3.bwd(df)
+        dcat = self.conv3.bwd(tape, df)
         del df
         # aux head (its logits also feed the region softmax)
         dlog_aux = self._head_dlogit(daux32, sv["aux32"], h, w)
         dlog_aux += dlog_gather.reshape(B, 1, h, w)
         da = self._logit_head_bwd(self.aux2, dlog_aux, sv["a"])
-        self.aux0.bwd(da, dx_out=dcat, dx_acc=True)
+        self.aux0.bwd(tape, da, dx_out=dcat, dx_acc=True)
         return dcat
 
-    def _backbone_bwd(self, dcat, ysz, need_dxin=True):
+    def _backbone_bwd(self, dcat, tape, need_dxin=True):
         e = self.eng
-        B = dcat.N
+        B, ysz = dcat.N, tape.pop("ysz")
         # concat -> branch gradients
         dys = [dcat.slice(0, self.chans[0])]
         off = self.chans[0]
@@ -455,7 +418,7 @@ class HRNetOCR:
         # stages, transitions
         for si in range(len(self.stages) - 1, -1, -1):
             for m in reversed(self.stages[si]):
-                dys = m.bwd(dys)
+                dys = m.bwd(tape, dys)
             tr = self.trans[si]
             n_prev = len(tr) - 1 if si > 0 else 1
             dprev = [None] * n_prev
@@ -469,12 +432,11 @@ class HRNetOCR:
                     continue
                 src = i if i < n_prev else n_prev - 1
                 if dprev[src] is None:
-                    dprev[src] = t.bwd(dys[i])
+                    dprev[src] = t.bwd(tape, dys[i])
                 else:
-                    t.bwd(dys[i], dx_out=dprev[src], dx_acc=True)
+                    t.bwd(tape, dys[i], dx_out=dprev[src], dx_acc=True)
             dys = dprev
         d = dys[0]
         for blk in reversed(self.layer1):
-            d = blk.bwd(d)
-        d = self.stem[1].bwd(d)
-        return self.stem[0].bwd(d, need_dx=need_dxin)
+            d = blk.bwd(tape, d)
+        return self.stem[0].bwd(tape, self.stem[1].bwd(tape, d), need_dx=need_dxin)

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from .. import _lib as L
 from ..engine import FM, Conv, ShuffleConv, grad_acc, pad8, _ptr
+from .blocks import act_bwd, sft_bwd
 from .shapes import CONV_SETTING
 
 A_NONE, A_RELU, A_LRELU, A_PRELU, A_SIG = L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU, L.ACT_PRELU, L.ACT_SIGMOID
@@ -374,16 +375,6 @@ class KBPN:
         return torch.where(take_up.reshape(B, 1, 1), self.U.unsqueeze(0), self.Z.unsqueeze(0))
 
     # ------------------------------------------------------------------ backward
-    def _act_bwd(self, conv, dout, out, res=None, res2=None, res_mode=L.RES_NONE, dres=None, dres_acc=False, dres2=None,
-                 dres2_acc=False, dpre=None):
-        """dOut -> dPre for a fused conv epilogue (in place unless ``dpre`` is given); accumulates bias / PReLU-slope grads."""
-        fz = conv.frozen
-        self.eng.epilogue_bwd(dout, out=out, act=conv.act, slope=conv.slope, prelu=conv.prelu, res=res, res2=res2, res_mode=res_mode,
-                              dpre=dout if dpre is None else dpre, dres=dres, dres_acc=dres_acc, dres2=dres2, dres2_acc=dres2_acc,
-                              dbias=None if (conv.b is None or fz) else grad_acc(conv.b),
-                              dprelu=None if (conv.prelu is None or fz) else grad_acc(conv.prelu), creal=conv.cout)
-        return dout if dpre is None else dpre
-
     def _wg(self, conv, dpre, x):
         if not conv.frozen:
             conv.bwd_weights(dpre, x)
@@ -424,23 +415,12 @@ class KBPN:
         for s in range(self.S, 0, -1):
             st, q = self.stages[s - 1], sv["stages"][s - 1]
             if s < self.S and self.sft:
-                # ---- SFT backward
-                fpre = concat_l.slice(0, 128 * s)
-                dfpre = dcl.slice(0, 128 * s)
-                dsc = e.new(B, h, w, 128 * s)
-                e.epilogue_bwd(dlowp, out=q["lowp"], res=fpre, res2=q["sc"], res_mode=L.RES_FMA, dpre=dlowp, dres=dfpre, dres_acc=True,
-                               dres2=dsc, dbias=None if st.sh1.frozen else grad_acc(st.sh1.b), creal=st.sh1.cout)
-                for c1, c0, t, dz, fold in ((st.sh1, st.sh0, q["t2"], dlowp, q["fold2"]), (st.sc1, st.sc0, q["t1"], None, q["fold1"])):
-                    if dz is None:
-                        dz = self._act_bwd(c1, dsc, q["sc"])
-                    self._wg(c1, dz, t)
-                    # conv0's LeakyReLU derivative rides on conv1's dgrad (mask = conv0's saved output) and its bias gradient comes out of
-                    # the border-class sums the folded weight gradient takes anyway: no epilogue-backward pass over the C-channel map
-                    dt = c1.bwd_input(dz, mask=(t, c0.slope))
-                    dvec_next = dvec_next + c0.bwd_weights_folded(dt, fpre, fold, self.Mtap, frozen=c0.frozen, bias_grad=True)
-                    c0.bwd_input(dt, seg=0, out=dfpre, accumulate=True)
-                    del dt
-                del dsc, dlowp
+                # ---- SFT backward (blocks.sft_bwd); the kernel code's gradient joins the kernel vector's
+                saves = tuple(q[k] for k in ("t1", "fold1", "sc", "t2", "fold2", "lowp"))
+                for dcode in sft_bwd(st.sc0, st.sc1, st.sh0, st.sh1, saves, concat_l.slice(0, 128 * s), dlowp, self.Mtap,
+                                     dx=dcl.slice(0, 128 * s), dx_acc=True):
+                    dvec_next = dvec_next + dcode
+                del saves, dlowp
             derr = None
             if s < self.S:
                 # ---- DownBlock backward
@@ -452,23 +432,23 @@ class KBPN:
                     st.kb_conv.bwd_input(dlow_s, out32=derr, in_hw=(h, w))
                     lows = q["lowd"]
                 dl0 = e.new(B, h, w, 128)
-                self._act_bwd(st.down3, dlow_s, lows, res=q["l0"], res_mode=L.RES_ADD, dres=dl0)
+                act_bwd(st.down3, dlow_s, lows, res=q["l0"], res_mode=L.RES_ADD, dres=dl0)
                 self._wg(st.down3, dlow_s, q["dd"])
                 # (down_conv2's epilogue-backward pass -- PReLU derivative from dd + xd, bias / slope sums, d(xd) = -dOut -- rides on
                 # down_conv3's dgrad where the phase-decomposed kernel takes the launch)
                 dxd = dxdc.slice(128 * (S - 1 - s), 128 * (S - s)) if gather else e.new(B, H, W, 128)
                 ddd = st.down3.bwd_input(dlow_s, in_hw=(H, W), dact=(st.down2, q["dd"]), dres=(q["xd"], dxd, L.RES_SUB))
                 if not st.down3.last_fused:
-                    self._act_bwd(st.down2, ddd, q["dd"], res=q["xd"], res_mode=L.RES_SUB, dres=dxd)
+                    act_bwd(st.down2, ddd, q["dd"], res=q["xd"], res_mode=L.RES_SUB, dres=dxd)
                 self._wg(st.down2, ddd, q["l0"])
                 st.down2.bwd_input(ddd, out=dl0, accumulate=True, in_hw=(h, w))
                 del ddd
-                self._act_bwd(st.down1, dl0, q["l0"])
+                act_bwd(st.down1, dl0, q["l0"])
                 self._wg(st.down1, dl0, q["xd"])
                 st.down1.bwd_input(dl0, out=dxd, accumulate=True, in_hw=(H, W), dact=(st.down_conv, q["xd"]))
                 del dl0
                 if not st.down1.last_fused:
-                    self._act_bwd(st.down_conv, dxd, q["xd"])
+                    act_bwd(st.down_conv, dxd, q["xd"])
                 chp = concat_h.slice(0, 128 * s)
                 self._wg(st.down_conv, dxd, chp)
                 if not gather:
@@ -496,7 +476,7 @@ class KBPN:
                     # read back as hs - h; dPre, the weight gradient and the slope gradient leave together
                     st.kb_up.bwd_thin_tp_fused(dhs, q["err16"], dpk, frozen=st.kb_up.frozen)
                 else:
-                    self._act_bwd(st.kb_up, dhs, hs, res=q["h"], res_mode=L.RES_ADD, dpre=dpk)
+                    act_bwd(st.kb_up, dhs, hs, res=q["h"], res_mode=L.RES_ADD, dpre=dpk)
                     self._wg(st.kb_up, dpk, q["err16"])
                 derr = e.f32(B, 3, h, w, zero=False)
                 st.kb_up.bwd_input(dpk, out32=derr, in_hw=(h, w))
@@ -538,25 +518,25 @@ class KBPN:
                 dpu, dh0 = dh, spare
             else:
                 dpu = spare
-                self._act_bwd(st.up3, dh, q["h"], res=q["h0"], res_mode=L.RES_ADD, dpre=dpu)
+                act_bwd(st.up3, dh, q["h"], res=q["h0"], res_mode=L.RES_ADD, dpre=dpu)
                 dh0 = dh
             del spare
             self._wg(st.up3, dpu, q["d"])
             dd_ = st.up3.bwd_input(dpu, in_hw=(h, w))
             del dh, dpu
             dxu = e.new(B, h, w, 128)
-            self._act_bwd(st.up2, dd_, q["d"], res=q["xu"], res_mode=L.RES_SUB, dres=dxu)
+            act_bwd(st.up2, dd_, q["d"], res=q["xu"], res_mode=L.RES_SUB, dres=dxu)
             self._wg(st.up2, dd_, q["h0"])
             # (the dgrad that completes dh0 also applies up1's PReLU derivative and sums its bias / slope gradients where the
             # phase-decomposed kernel takes the launch: no epilogue-backward pass over the HR map)
             st.up2.bwd_input(dd_, out=dh0, accumulate=True, in_hw=(H, W), dact=(st.up1, q["h0"]))
             del dd_
             if not st.up2.last_fused:
-                self._act_bwd(st.up1, dh0, q["h0"])
+                act_bwd(st.up1, dh0, q["h0"])
             self._wg(st.up1, dh0, q["xu"])
             st.up1.bwd_input(dh0, out=dxu, accumulate=True, in_hw=(h, w))
             del dh0
-            self._act_bwd(st.up_conv, dxu, q["xu"])
+            act_bwd(st.up_conv, dxu, q["xu"])
             self._wg(st.up_conv, dxu, q["low_in"])
             if self.sft or s == 1:
                 dlowp = st.up_conv.bwd_input(dxu)        # gradient wrt this stage's `low` input
@@ -589,7 +569,7 @@ class KBPN:
             for i in (2, 1, 0):
                 c = self.pred[i]
                 if i < 2:
-                    self._act_bwd(c, dz, zs[i + 1])
+                    act_bwd(c, dz, zs[i + 1])
                 self._wg(c, dz, zs[i])
                 if i > 0:
                     dz = c.bwd_input(dz)
@@ -598,7 +578,7 @@ class KBPN:
         d = dinit
         for i in (3, 2, 1, 0):
             c = self.feat[i]
-            self._act_bwd(c, d, feats[i + 1])
+            act_bwd(c, d, feats[i + 1])
             self._wg(c, d, feats[i])
             if i > 0:
                 d = c.bwd_input(d)

@@ -3,35 +3,20 @@
 Counterpart of /root/reference/model/modeling/pspnet_pytorch/pspnet.py:23-123 and extractors.py:41-70,
 112-161 with the reference's parameter names; train-mode BatchNorm statistics come from the conv
 epilogue, Dropout2d channel masks are fused into the following resize / BN-apply, the PSP concat buffer is
-written in place by its producers.  Explicit backward.
+written in place by its producers.  Explicit backward; what it needs rides on a per-forward tape (blocks.py).
 """
-import ctypes as C
 import os
 
 import torch
 
 from .. import _lib as L
-from ..engine import FM, Conv, BatchNorm, grad_acc, pad8, _ptr
+from ..engine import FM, Conv, _ptr
+from .blocks import ConvBN, act_bwd, sft_bwd
+from .kbpn import border_tap_mask
 from .shapes import RESNET34
 
 DROP_P = {"drop_1": 0.3, "drop_2a": 0.15, "drop_2b": 0.15, "drop_2c": 0.15, "aux_drop": 0.1}   # pspnet.py:67,73,83
 DROP_C = {"drop_1": 1024, "drop_2a": 256, "drop_2b": 64, "drop_2c": 64, "aux_drop": 256}
-
-
-class ConvBN:
-    def __init__(self, eng, P, conv_name, bn_name, cin, cout, k, stride, pad, dil=1, bias=False):
-        self.conv = Conv(eng, conv_name, P, k, stride, pad, dil, bias=bias, act=L.ACT_NONE)
-        self.bn = BatchNorm(eng, bn_name, P, cout)
-        self.eng = eng
-
-    def fwd(self, x, training=True):
-        if not training:                # eval: running statistics (F.batch_norm(training=False))
-            raw = self.conv.fwd(x)
-            return raw, self.bn.rmean, torch.rsqrt(self.bn.rvar + 1e-5)
-        stat = self.bn.new_stat()
-        raw = self.conv.fwd(x, stat=stat, stat_mode=L.STAT_BN)
-        mean, invstd = self.bn.finalize(stat, raw.npix, update_running=training)
-        return raw, mean, invstd
 
 
 class _SFTLike:
@@ -49,6 +34,34 @@ class _SFTLike:
         return [self.sc0, self.sc1, self.sh0, self.sh1]
 
 
+class _ResBlock:
+    """BasicBlock of the dilated ResNet (extractors.py:41-70): relu(bn2(conv2(relu(bn1(conv1(x))))) + downsample(x))"""
+
+    def __init__(self, eng, P, pre, stride, dil, down, layer):
+        self.eng, self.layer = eng, layer
+        self.c1 = ConvBN(eng, P, pre + ".conv1", pre + ".bn1", 3, stride, dil, dil)
+        self.c2 = ConvBN(eng, P, pre + ".conv2", pre + ".bn2", 3, 1, dil, dil)
+        self.down = ConvBN(eng, P, pre + ".downsample.0", pre + ".downsample.1", 1, stride, 0, act=L.ACT_NONE) if down else None
+
+    def units(self):
+        return [self.c1, self.c2] + ([self.down] if self.down else [])
+
+    def fwd(self, x, training, tape, out=None):
+        a1 = self.c1.fwd(x, training, tape)
+        pre = self.c2.conv_stats(a1, training)
+        res = self.down.fwd(x, training, tape) if self.down else x
+        return self.c2.fwd(a1, training, tape, res=res, out=out, pre=pre)
+
+    def bwd(self, tape, dy):
+        dres = self.eng.new(dy.N, dy.H, dy.W, dy.c)
+        da1 = self.c2.bwd(tape, dy, dres=dres)
+        g1 = self.c1.bwd_bn(tape, da1)
+        del da1
+        dx = self.down.bwd(tape, dres) if self.down else dres       # the downsample chain between c1's wgrad and its (accumulating) dgrad
+        self.c1.bwd_dx(g1, out=dx, acc=True)
+        return dx
+
+
 class PSPNet:
     drop_keys = tuple(DROP_P)
 
@@ -58,40 +71,29 @@ class PSPNet:
         self.eng, self.P, self.prefix = eng, params, prefix
         self.blur_dim = blur_dim
         self.blur_skip = []
+        e, P, f = eng, params, prefix + ".feats"
         if blur_dim is not None:
             for i in range(2):
-                self.blur_skip.append((_SFTLike(eng, params, f"{prefix}.blur_skip.{2 * i}", 64, blur_dim),
-                                       ConvBN(eng, params, f"{prefix}.blur_skip.{2 * i + 1}.layer", f"{prefix}.blur_skip.{2 * i + 1}.norm",
-                                              64, 64, 3, 1, 1)))
-            m = torch.ones(4, 3)
-            m[2, 0] = m[3, 0] = 0.0          # first row/col: tap 0 reads outside
-            m[1, 2] = m[3, 2] = 0.0          # last row/col: tap 2 reads outside
-            self.Mtap = m.to(eng.device)
-        e, P, f = eng, params, prefix + ".feats"
-        self.stem = ConvBN(e, P, f + ".conv1", f + ".bn1", 3, 64, 7, 2, 3)
+                bs = f"{prefix}.blur_skip.{2 * i + 1}"
+                self.blur_skip.append((_SFTLike(e, P, f"{prefix}.blur_skip.{2 * i}", 64, blur_dim), ConvBN(e, P, bs + ".layer", bs + ".norm", 3)))
+            self.Mtap = border_tap_mask().to(eng.device)
+        self.stem = ConvBN(e, P, f + ".conv1", f + ".bn1", 7, 2)
         self.blocks = []
         inpl = 64
         for li, (planes, nblk, stride, dil) in enumerate(RESNET34, 1):
             for b in range(nblk):
-                bp = f"{f}.layer{li}.{b}"
-                first = b == 0
-                s_, d_ = (stride, 1) if first else (1, dil)
-                blk = {"c1": ConvBN(e, P, bp + ".conv1", bp + ".bn1", inpl if first else planes, planes, 3, s_, d_, d_),
-                       "c2": ConvBN(e, P, bp + ".conv2", bp + ".bn2", planes, planes, 3, 1, d_, d_),
-                       "down": None, "layer": li}
-                if first and (stride != 1 or inpl != planes):
-                    blk["down"] = ConvBN(e, P, bp + ".downsample.0", bp + ".downsample.1", inpl, planes, 1, stride, 0)
-                self.blocks.append(blk)
+                s_, d_ = (stride, 1) if b == 0 else (1, dil)
+                self.blocks.append(_ResBlock(e, P, f"{f}.layer{li}.{b}", s_, d_, b == 0 and (stride != 1 or inpl != planes), li))
             inpl = planes
+        self.x3_block = [b for b in self.blocks if b.layer == 3][-1]       # its output feeds the aux head
         self.psp_convs = [Conv(e, f"{prefix}.psp.stages.{i}.1", P, 1, bias=False) for i in range(4)]
         self.bottleneck = Conv(e, prefix + ".psp.bottleneck", P, 1, bias=True, act=L.ACT_RELU)
-        self.ups = [ConvBN(e, P, f"{prefix}.{n}.conv.0", f"{prefix}.{n}.conv.1", ci, co, 3, 1, 1, bias=True)
-                    for n, ci, co in (("up_1", 1024, 256), ("up_2", 256, 64), ("up_3", 64, 64))]
-        self.up_prelu = [P[f"{prefix}.{n}.conv.2.weight"] for n in ("up_1", "up_2", "up_3")]
+        self.ups = [ConvBN(e, P, f"{prefix}.{n}.conv.0", f"{prefix}.{n}.conv.1", 3, bias=True, act=L.ACT_PRELU, prelu=P[f"{prefix}.{n}.conv.2.weight"])
+                    for n in ("up_1", "up_2", "up_3")]
         self.final = Conv(e, prefix + ".final.0", P, 1, bias=True, act=L.ACT_SIGMOID)
-        self.aux0 = ConvBN(e, P, prefix + ".aux.0", prefix + ".aux.1", 256, 256, 3, 1, 1)
+        self.aux0 = ConvBN(e, P, prefix + ".aux.0", prefix + ".aux.1", 3)
         self.aux4 = Conv(e, prefix + ".aux.4", P, 1, bias=True, act=L.ACT_SIGMOID)
-        self.saved = None
+        self.saved = None       # the tape of the last training forward (None otherwise); the train step moves it to its autograd node
         # "split": every forward activation of the detector is an fp16 hi + lo pair (~22 mantissa bits) and every forward conv runs
         # three MFMA passes (x_hi w_hi + x_lo w_hi + x_hi w_lo) in one fp32 accumulator; the backward reads the hi planes (BatchNorm /
         # max-pool backward also the lo planes, so their masks are the forward's).  Set by the model (detector_precision).
@@ -102,7 +104,7 @@ class PSPNet:
         self.split_tail_plain = int(os.environ.get("CSBSR_SPLIT_TAIL_PLAIN", "0"))
 
     def all_convs(self):
-        cs = [self.stem.conv] + [b[k].conv for b in self.blocks for k in ("c1", "c2", "down") if b[k] is not None]
+        cs = [u.conv for u in [self.stem] + [u for b in self.blocks for u in b.units()]]
         cs += self.psp_convs + [self.bottleneck] + [u.conv for u in self.ups] + [self.final, self.aux0.conv, self.aux4]
         for sft, cb in self.blur_skip:
             cs += sft.convs() + [cb.conv]
@@ -124,41 +126,24 @@ class PSPNet:
     # ------------------------------------------------------------------ forward
     def forward(self, xin, drop, training=True, kvec=None):
         """xin: FM [B,H,W,8] (3 real channels, already normalised); kvec [B, blur_dim] fp32 for the BlurSkip variant.
-        Returns (seg32, aux32) fp32 [B,1,H,W]."""
+        Returns (seg32, aux32) fp32 [B,1,H,W].  A training forward with gradients enabled leaves its tape in ``self.saved``."""
         e = self.eng
         B, H, W = xin.N, xin.H, xin.W
-        sv = {"xin": xin, "drop": drop}
-        keep_trunk = self.blur_dim is None      # BlurSkip: the trunk is frozen, nothing of it is needed by the backward
-        raw, m, iv = self.stem.fwd(xin, training)
-        a = self.stem.bn.apply(raw, m, iv, act=L.ACT_RELU)
+        tape = {} if training and torch.is_grad_enabled() else None
+        trunk = tape if self.blur_dim is None else None      # BlurSkip: the trunk is frozen, nothing of it is needed by the backward
+        a = self.stem.fwd(xin, training, trunk)
         PH, PW = (a.H + 2 - 3) // 2 + 1, (a.W + 2 - 3) // 2 + 1
-        p = e.new(B, PH, PW, 64, split=bool(a.lo))
-        L.call("csbsr_maxpool3x3s2_fwd_split", _ptr(a.t), a.ld, a.lo, _ptr(p.t), p.ld, p.lo, B, a.H, a.W, 64, e.stream)
-        sv["stem"] = (raw, m, iv, a, p)
-        x = p
-        bsv = []
-        x3 = None
-        nb = len(self.blocks)
-        for bi, blk in enumerate(self.blocks):
-            r1, m1, i1 = blk["c1"].fwd(x, training)
-            a1 = blk["c1"].bn.apply(r1, m1, i1, act=L.ACT_RELU)
-            r2, m2, i2 = blk["c2"].fwd(a1, training)
-            if blk["down"] is not None:
-                rd, md, idv = blk["down"].fwd(x, training)
-                res = blk["down"].bn.apply(rd, md, idv, act=L.ACT_NONE)
-                dsv = (rd, md, idv)
-            else:
-                res, dsv = x, None
+        x = e.new(B, PH, PW, 64, split=bool(a.lo))
+        L.call("csbsr_maxpool3x3s2_fwd_split", _ptr(a.t), a.ld, a.lo, _ptr(x.t), x.ld, x.lo, B, a.H, a.W, 64, e.stream)
+        pool = (a, x)
+        for blk in self.blocks:
             out = None
-            if bi == nb - 1:    # last block writes straight into the PSP concat buffer (channels 2048:2560)
-                cat = e.new(B, r2.H, r2.W, 2560, split=bool(r2.lo))
+            if blk is self.blocks[-1]:    # last block writes straight into the PSP concat buffer (channels 2048:2560)
+                cat = e.new(B, x.H, x.W, 2560, split=bool(x.lo))
                 out = cat.slice(2048, 2560)
-            y = blk["c2"].bn.apply(r2, m2, i2, act=L.ACT_RELU, res=res, out=out)
-            bsv.append((x, r1, m1, i1, a1, r2, m2, i2, res, dsv, y) if keep_trunk else None)
-            x = y
-            if blk["layer"] == 3 and (bi + 1 == nb or self.blocks[bi + 1]["layer"] == 4):
-                x3 = y
-        sv["blocks"] = bsv
+            x = blk.fwd(x, training, trunk, out=out)
+            if blk is self.x3_block:
+                x3 = x
         fH, fW = x.H, x.W
         # pyramid pooling
         psp = []
@@ -170,41 +155,36 @@ class PSPNet:
             e.bilinear(pc, fH, fW, False, out=cat.slice(512 * i, 512 * (i + 1)))
             psp.append((pooled, pc))
         bott = self.bottleneck.fwd(cat)
-        sv["psp"] = (cat, psp, bott)
         # upsample stages; the dropout that follows stage j is fused into stage j+1's resize (or the last BN apply)
         cur, cur_drop = bott, drop["drop_1"]
-        usv = []
-        names = ("drop_2a", "drop_2b", "drop_2c")
-        for j, up in enumerate(self.ups):
+        ups = []
+        for j, (up, name) in enumerate(zip(self.ups, ("drop_2a", "drop_2b", "drop_2c"))):
             if cur.lo and j >= len(self.ups) - self.split_tail_plain:
                 cur = FM(cur.t, cur.c, H=cur.H, W=cur.W)          # the hi plane alone: this stage and everything after it is plain fp16
             u = e.bilinear(cur, cur.H * 2, cur.W * 2, False, drop=cur_drop)
-            raw, m, iv = up.fwd(u, training)
-            last = j == 2
-            y = up.bn.apply(raw, m, iv, act=L.ACT_PRELU, prelu=self.up_prelu[j], drop=drop[names[j]] if last else None)
-            usv.append((cur, cur_drop, u, raw, m, iv, y) if keep_trunk else None)
-            cur, cur_drop = y, drop[names[j]]
-        sv["ups"] = usv
+            ups.append((cur, cur_drop))
+            cur, cur_drop = up.fwd(u, training, trunk, drop=drop[name] if j == 2 else None), drop[name]
+        if trunk is not None:
+            tape.update(pool=pool, psp=(cat, psp, bott), ups=ups)
         if self.blur_dim is not None:
-            cur = self._blur_skip_fwd(cur, kvec, training, sv)
+            cur = self._blur_skip_fwd(cur, kvec, training, tape)
         seg32 = e.f32(B, 1, H, W, zero=False)
         self.final.fwd(cur, out32=seg32)
         # aux head on layer3 output
-        ra, ma, ia = self.aux0.fwd(x3, training)
-        aa = self.aux0.bn.apply(ra, ma, ia, act=L.ACT_RELU, drop=drop["aux_drop"])
+        aa = self.aux0.fwd(x3, training, trunk, drop=drop["aux_drop"])
         aux_lo = e.f32(B, 1, x3.H, x3.W, zero=False)
         self.aux4.fwd(aa, out32=aux_lo)
         aux32 = e.f32(B, 1, H, W, zero=False)
         L.call("csbsr_bilinear32_fwd", _ptr(aux_lo), _ptr(aux32), B, x3.H, x3.W, H, W, 1, e.stream)
-        sv["aux"] = (x3, ra, ma, ia, aa, aux_lo)
-        sv["seg32"], sv["p3"] = seg32, cur
-        if not keep_trunk:
-            sv["stem"] = sv["psp"] = sv["aux"] = None
-        self.saved = sv
+        if tape is not None:
+            tape.update(seg32=seg32, p3=cur)
+        if trunk is not None:
+            tape["aux"] = (aa, aux_lo)
+        self.saved = tape
         return seg32, aux32
 
     # ------------------------------------------------------------------ BlurSkip branch (pspnet.py:191-198)
-    def _blur_skip_fwd(self, p, kvec, training, sv):
+    def _blur_skip_fwd(self, p, kvec, training, tape):
         e = self.eng
         q, bsv = p, []
         for sft, cb in self.blur_skip:
@@ -212,57 +192,26 @@ class PSPNet:
             sc = sft.sc1.fwd(t1)
             t2, f2 = sft.sh0.fwd_folded(q, kvec, self.Mtap)
             y = sft.sh1.fwd(t2, res=q, res2=sc, res_mode=L.RES_FMA)              # q * scale + shift
-            raw, m, iv = cb.fwd(y, training)
-            z = cb.bn.apply(raw, m, iv, act=L.ACT_RELU)
-            bsv.append((q, t1, f1, sc, t2, f2, y, raw, m, iv, z))
-            q = z
+            bsv.append((q, (t1, f1, sc, t2, f2, y)))
+            q = cb.fwd(y, training, tape)
         out = e.new(p.N, p.H, p.W, p.c, split=bool(p.lo))
         L.call("csbsr_axpby_split", p.npix, p.cp, _ptr(p.t), p.ld, p.lo, 1.0, _ptr(q.t), q.ld, q.lo, 1.0, _ptr(out.t), out.ld, out.lo,
                e.stream)    # p + _p
-        sv["blur_skip"] = bsv
+        if tape is not None:
+            tape["blur_skip"] = bsv
         return out
 
-    def _blur_skip_bwd(self, d):
+    def _blur_skip_bwd(self, tape, d):
         """d: gradient wrt (p + _p).  Accumulates the blur_skip.* gradients; nothing upstream of it is trainable."""
-        e = self.eng
-        bsv = self.saved["blur_skip"]
-
-        def act_bwd(conv, dout, out):
-            e.epilogue_bwd(dout, out=out, act=conv.act, slope=conv.slope, prelu=conv.prelu, dpre=dout, dbias=grad_acc(conv.b),
-                           dprelu=None if conv.prelu is None else grad_acc(conv.prelu), creal=conv.cout)
-            return dout
-
+        bsv = tape.pop("blur_skip")
         for i in (1, 0):
             sft, cb = self.blur_skip[i]
-            q, t1, f1, sc, t2, f2, y, raw, m, iv, z = bsv[i]
-            bsv[i] = None
-            draw = cb.bn.backward(d, raw, m, iv, act=L.ACT_RELU)
-            cb.conv.bwd_weights(draw, y)
-            dy = cb.conv.bwd_input(draw)
-            del draw, d
-            need_dq = i > 0                   # block 0's input is the frozen trunk's output
-            dq = e.new(q.N, q.H, q.W, q.c) if need_dq else None
-            dsc = e.new(q.N, q.H, q.W, q.c)
-            e.epilogue_bwd(dy, out=y, res=q, res2=sc, res_mode=L.RES_FMA, dpre=dy, dres=dq, dres2=dsc, dbias=grad_acc(sft.sh1.b),
-                           creal=sft.sh1.cout)
-            for c1, c0, t, dz, fold in ((sft.sh1, sft.sh0, t2, dy, f2), (sft.sc1, sft.sc0, t1, None, f1)):
-                if dz is None:
-                    dz = act_bwd(c1, dsc, sc)
-                c1.bwd_weights(dz, t)
-                if t.H >= 3 and t.W >= 3 and t.H * t.W >= 1024 and e.fold_prelu and e.prelu_fold_ok(c0.prelu):      # (csbsr_border_class_sums_prelu's own precondition; a slope safely > 0)
-                    # conv0's PReLU derivative rides on conv1's dgrad (mask = conv0's saved output, slope read on the device); its bias
-                    # gradient is the sum of the border-class sums the folded weight gradient takes anyway, its slope gradient comes out
-                    # of the same pass over (dPre, t): no epilogue-backward pass over the 505-channel HR map (8.5 ms each at B = 4)
-                    dt = c1.bwd_input(dz, mask=(t, c0.prelu))
-                    c0.bwd_weights_folded(dt, q, fold, self.Mtap, bias_grad=True, prelu_out=t)
-                else:
-                    dt = c1.bwd_input(dz)
-                    act_bwd(c0, dt, t)
-                    c0.bwd_weights_folded(dt, q, fold, self.Mtap)
-                if need_dq:
-                    c0.bwd_input(dt, seg=0, out=dq, accumulate=True)
-                del dt
-            del dy, dsc
+            q, saves = bsv.pop()
+            dy = cb.bwd(tape, d)
+            del d
+            dq = self.eng.new(q.N, q.H, q.W, q.c) if i > 0 else None      # block 0's input is the frozen trunk's output
+            sft_bwd(sft.sc0, sft.sc1, sft.sh0, sft.sh1, saves, q, dy, self.Mtap, dx=dq)
+            del dy, saves
             d = dq
 
     # ------------------------------------------------------------------ backward
@@ -273,89 +222,55 @@ class PSPNet:
         dpre = e.new(B, H, W, 1)
         L.call("csbsr_sigmoid_bwd_to_nhwc8", _ptr(dprob32), _ptr(prob32), _ptr(dpre.t), B * H * W, 1.0, e.stream)
         if not frozen:
-            e.epilogue_bwd(dpre, dbias=grad_acc(conv.b), creal=1)
+            act_bwd(conv, dpre)
             conv.bwd_weights(dpre, x)
         return conv.bwd_input(dpre)
 
     def backward(self, dseg32, daux32, need_dxin=True):
         """Gradients (scaled) wrt the two probability maps -> returns FM gradient wrt xin [B,H,W,8]; ``need_dxin=False`` (the input is no
-        function of a parameter: MODEL.SR="bicubic") skips the stem's input gradient and returns None."""
-        e, sv = self.eng, self.saved
-        drop = sv["drop"]
-        xin = sv["xin"]
-        B, H, W = xin.N, xin.H, xin.W
+        function of a parameter: MODEL.SR="bicubic") skips the stem's input gradient and returns None.  Consumes ``self.saved``."""
+        e = self.eng
+        tape, self.saved = self.saved, None
+        B, _, H, W = dseg32.shape
         if self.blur_dim is not None:
-            self._blur_skip_bwd(self._sigmoid_head_bwd(self.final, dseg32, sv["seg32"], sv["p3"], frozen=True))
-            self.saved = None
+            self._blur_skip_bwd(tape, self._sigmoid_head_bwd(self.final, dseg32, tape.pop("seg32"), tape.pop("p3"), frozen=True))
             return None
         # aux head
-        x3, ra, ma, ia, aa, aux_lo = sv["aux"]
-        daux_lo = e.f32(B, 1, x3.H, x3.W, zero=False)
-        L.call("csbsr_bilinear32_bwd", _ptr(daux32), _ptr(daux_lo), B, x3.H, x3.W, H, W, 1, e.stream)
-        daa = self._sigmoid_head_bwd(self.aux4, daux_lo, aux_lo, aa)
-        dra = self.aux0.bn.backward(daa, ra, ma, ia, act=L.ACT_RELU, drop=drop["aux_drop"])
-        self.aux0.conv.bwd_weights(dra, x3)
-        dx3_aux = self.aux0.conv.bwd_input(dra)
-        del daa, dra
-        # main head
-        d = self._sigmoid_head_bwd(self.final, dseg32, sv["seg32"], sv["p3"])
-        names = ("drop_2a", "drop_2b", "drop_2c")
-        for j in (2, 1, 0):
-            cur, cur_drop, u, raw, m, iv, y = sv["ups"][j]
-            up = self.ups[j]
-            draw = up.bn.backward(d, raw, m, iv, act=L.ACT_PRELU, prelu=self.up_prelu[j], drop=drop[names[j]] if j == 2 else None,
-                                  dprelu=grad_acc(self.up_prelu[j]))
-            up.conv.bwd_weights(draw, u)
-            grad_acc(up.conv.b)          # a conv bias feeding train-mode BN has an identically zero gradient (not None)
-            du = up.conv.bwd_input(draw)
+        aa, aux_lo = tape.pop("aux")
+        daux_lo = e.f32(B, 1, *aux_lo.shape[2:], zero=False)
+        L.call("csbsr_bilinear32_bwd", _ptr(daux32), _ptr(daux_lo), B, *aux_lo.shape[2:], H, W, 1, e.stream)
+        dx3_aux = self.aux0.bwd(tape, self._sigmoid_head_bwd(self.aux4, daux_lo, aux_lo, aa))
+        del aa
+        # main head, upsample stages
+        d = self._sigmoid_head_bwd(self.final, dseg32, tape.pop("seg32"), tape.pop("p3"))
+        ups = tape.pop("ups")
+        for up in reversed(self.ups):
+            cur, cur_drop = ups.pop()
+            du = up.bwd(tape, d)
             d = e.new(B, cur.H, cur.W, cur.c)
             e.bilinear_bwd(du, d, False, False, drop=cur_drop)
-            del draw, du
-        cat, psp, bott = sv["psp"]
-        self.eng.epilogue_bwd(d, out=bott, act=L.ACT_RELU, dpre=d, dbias=grad_acc(self.bottleneck.b), creal=1024)
+            del du, cur
+        cat, psp, bott = tape.pop("psp")
+        act_bwd(self.bottleneck, d, bott)
         self.bottleneck.bwd_weights(d, cat)
         dcat = self.bottleneck.bwd_input(d)
-        del d
+        del d, bott
         fH, fW = cat.H, cat.W
-        df = dcat.slice(2048, 2560)
+        dy = dcat.slice(2048, 2560)
         for i, size in enumerate((1, 2, 3, 6)):
             pooled, pc = psp[i]
             dpc = e.new(B, size, size, 512)
             e.bilinear_bwd(dcat.slice(512 * i, 512 * (i + 1)), dpc, False, False)
             self.psp_convs[i].bwd_weights(dpc, pooled)
             dpool = self.psp_convs[i].bwd_input(dpc)
-            L.call("csbsr_adaptive_avgpool_bwd", _ptr(dpool.t), _ptr(df.t), df.ld, 1, B, fH, fW, 512, size, size, e.stream)
-        dy = df
-        nb = len(self.blocks)
-        for bi in range(nb - 1, -1, -1):
-            blk = self.blocks[bi]
-            x, r1, m1, i1, a1, r2, m2, i2, res, dsv, y = sv["blocks"][bi]
-            if blk["layer"] == 3 and (bi + 1 == nb or self.blocks[bi + 1]["layer"] == 4):
+            L.call("csbsr_adaptive_avgpool_bwd", _ptr(dpool.t), _ptr(dy.t), dy.ld, 1, B, fH, fW, 512, size, size, e.stream)
+        del cat, psp
+        for blk in reversed(self.blocks):
+            if blk is self.x3_block:       # the aux head's gradient joins where its input was tapped
                 L.call("csbsr_axpby", dy.npix, dy.cp, _ptr(dy.t), dy.ld, 1.0, _ptr(dx3_aux.t), dx3_aux.ld, 1.0, _ptr(dy.t), dy.ld, e.stream)
-            dres = e.new(B, res.H, res.W, res.c)
-            dr2 = blk["c2"].bn.backward(dy, r2, m2, i2, act=L.ACT_RELU, res=res, dres=dres)
-            blk["c2"].conv.bwd_weights(dr2, a1)
-            da1 = blk["c2"].conv.bwd_input(dr2)
-            dr1 = blk["c1"].bn.backward(da1, r1, m1, i1, act=L.ACT_RELU)
-            blk["c1"].conv.bwd_weights(dr1, x)
-            del dr2, da1
-            if blk["down"] is not None:
-                rd, md, idv = dsv
-                drd = blk["down"].bn.backward(dres, rd, md, idv, act=L.ACT_NONE)
-                blk["down"].conv.bwd_weights(drd, x)
-                dx = blk["down"].conv.bwd_input(drd, in_hw=(x.H, x.W))
-                blk["c1"].conv.bwd_input(dr1, out=dx, accumulate=True, in_hw=(x.H, x.W))
-            else:
-                dx = dres
-                blk["c1"].conv.bwd_input(dr1, out=dx, accumulate=True, in_hw=(x.H, x.W))
-            dy = dx
-            sv["blocks"][bi] = None
-        raw, m, iv, a, p = sv["stem"]
+            dy = blk.bwd(tape, dy)
+        a, p = tape.pop("pool")
         da = e.new(B, a.H, a.W, 64)
         assert dy.flat_ok() and dy.ld == dy.cp
         L.call("csbsr_maxpool3x3s2_bwd_split", _ptr(a.t), a.ld, a.lo, _ptr(p.t), p.ld, p.lo, _ptr(dy.t), _ptr(da.t), B, a.H, a.W, 64, e.stream)
-        draw = self.stem.bn.backward(da, raw, m, iv, act=L.ACT_RELU)
-        self.stem.conv.bwd_weights(draw, xin)
-        dxin = self.stem.conv.bwd_input(draw, in_hw=(H, W)) if need_dxin else None
-        self.saved = None
-        return dxin
+        return self.stem.bwd(tape, da, need_dx=need_dxin)

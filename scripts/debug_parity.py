@@ -46,26 +46,24 @@ with torch.no_grad():
     bn = O.BNState(P, True)
     xn = O.norm_sr(t("sr_preds"), pc)
     show("xin", fm2nchw(xin), xn)
-    psp = rt["psp"].saved
+    net, psp = rt["psp"], rt["psp"].saved      # the tape: a unit's entry is (x, raw, mean, invstd, res, drop)
     pre = "segmentation_model.feats"
     import torch.nn.functional as F
     c1 = F.conv2d(xn, P[pre + ".conv1.weight"], None, 2, 3)
-    show("stem raw", fm2nchw(psp["stem"][0]), c1)
-    a = F.relu(bn(pre + ".bn1", c1)); show("stem act", fm2nchw(psp["stem"][3]), a)
-    p = F.max_pool2d(a, 3, 2, 1); show("pool", fm2nchw(psp["stem"][4]), p)
+    show("stem raw", fm2nchw(psp[net.stem][1]), c1)
+    a = F.relu(bn(pre + ".bn1", c1)); show("stem act", fm2nchw(psp["pool"][0]), a)
+    p = F.max_pool2d(a, 3, 2, 1); show("pool", fm2nchw(psp["pool"][1]), p)
     f, x3 = O.resnet34_dilated(P, O.BNState(P, True), xn)
-    show("layer4 out", fm2nchw(psp["blocks"][-1][-1]), f)
-    show("layer3 out", fm2nchw(psp["aux"][0]), x3)
-    for bi in range(len(psp["blocks"])):
-        pass
+    show("layer4 out", fm2nchw(psp["psp"][0].slice(2048, 2560)), f)
+    show("layer3 out", fm2nchw(psp[net.aux0][0]), x3)
     pm = O.psp_module(P, f)
     show("psp bott", fm2nchw(psp["psp"][2]), pm)
     u1 = O.psp_upsample(P, O.BNState(P, True), "segmentation_model.up_1", pm)
-    show("up1", fm2nchw(psp["ups"][0][6]), u1)
+    show("up1", fm2nchw(psp["ups"][1][0]), u1)
     u2 = O.psp_upsample(P, O.BNState(P, True), "segmentation_model.up_2", u1)
-    show("up2", fm2nchw(psp["ups"][1][6]), u2)
+    show("up2", fm2nchw(psp["ups"][2][0]), u2)
     u3 = O.psp_upsample(P, O.BNState(P, True), "segmentation_model.up_3", u2)
-    show("up3", fm2nchw(psp["ups"][2][6]), u3)
+    show("up3", fm2nchw(psp["p3"]), u3)
     main, aux = O.pspnet_forward(P, xn, O.BNState(P, True))
     show("seg (oracle same in)", seg32.cpu(), main)
     show("aux", aux32.cpu(), aux)

@@ -175,8 +175,9 @@ def test_hr_module_vs_oracle(split):
     m, rt = _model()
     gs = 1024.0
     mod = _HRModule(rt["eng"], rt["P"], pre, chans)
-    ys = mod.fwd([_fm(x, split) for x in xs], True)
-    dxs = mod.bwd([_fm(r * gs) for r in rs])
+    tape = {}
+    ys = mod.fwd([_fm(x, split) for x in xs], True, tape)
+    dxs = mod.bwd(tape, [_fm(r * gs) for r in rs])
     torch.cuda.synchronize()
     tol_y, tol_g = (1e-3, 3e-2) if split else (1e-2, 0.25)
     for i in range(4):
@@ -210,8 +211,9 @@ def test_ocr_head_vs_oracle(split):
     m, rt = _model()
     net = rt["psp"]
     gs = float(2 ** round(np.log2(B * H * H)))
-    seg, aux = net._head_fwd(_fm(feats, split), {"ocr_drop": keep.cuda().contiguous()}, True, H, H)
-    dcat = net._head_bwd((r1 * gs).cuda().contiguous(), (r2 * gs).cuda().contiguous())
+    tape = {}
+    seg, aux = net._head_fwd(_fm(feats, split), {"ocr_drop": keep.cuda().contiguous()}, True, H, H, tape)
+    dcat = net._head_bwd((r1 * gs).cuda().contiguous(), (r2 * gs).cuda().contiguous(), tape)
     torch.cuda.synchronize()
     print("head: seg %.2e aux %.2e dcat %.2e" % (max_rel_to_scale(seg.cpu(), seg_o.detach()), max_rel_to_scale(aux.cpu(), aux_o.detach()),
                                                 rel_err(_from_fm(dcat) / gs, fr.grad)))
