@@ -149,6 +149,8 @@ SIGNATURES = {
     "csbsr_aa_bicubic_up": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_aa_bicubic_down_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "csbsr_aa_bicubic_down_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "csbsr_area_down_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "csbsr_area_down_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "csbsr_blur_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
     "csbsr_blur_bwd_input": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_blur_bwd_kernel": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -115,4 +115,17 @@ def path_config(c, antialias=True):
     p.kernel_sft = bool(c.MODEL.KBPN_KERNEL_SFT)                         # kbpn.py:165,169-171,190: False = no SFT layer between the stages
     p.zero_pad_kernel = bool(c.MODEL.ZERO_PAD_KERNEL)                    # kbpn.py:543-554,583-596: per-sample choice zero-pad / bicubic for the 7x7 -> 21x21 kernel update
     p.lr_error = str(c.MODEL.SUM_LR_ERROR_POS) == "LR"                   # kbpn.py:166,174-187,369-374,404-409: back-projection error added at LR
+    # train.py:43, transforms.py:505-531: FactorResize's mode, "bicubic" or "area", of the datasets' LR image and of KBPNLoss's pseudo-LR;
+    # carried as written -- the model constructors refuse any other value (check_downscale)
+    p.downscale = c.SOLVER.get("DOWNSCALE_INTERPOLATION", "bicubic")
     return p
+
+
+DOWNSCALE_MODES = ("bicubic", "area")
+
+
+def check_downscale(name, what="interpolation", error=ValueError):
+    """``name`` if it is one of FactorResize's two modes (transforms.py:518-531; the reference exits on any other), else ``error``."""
+    if name not in DOWNSCALE_MODES:
+        raise error(f"{what}={name!r}: 'bicubic' or 'area'")
+    return name

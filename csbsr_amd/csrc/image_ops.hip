@@ -658,6 +658,120 @@ extern "C" int csbsr_aa_bicubic_down_bwd(const float* dy, float* dx, int32_t acc
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------- area down-scale
+// FactorResize('area') = F.interpolate(mode='area') by an integer factor f (transforms.py:505-531): the mean of the f x f window,
+//   y[p,oy,ox] = (sum_{a<f} sum_{b<f} x[p, oy*f+a, ox*f+b]) / (f*f),   dx[p,iy,ix] = dy[p,iy/f,ix/f] / (f*f).
+// The sum is ONE fp32 chain, a outer and b inner, then one division: that is the order the CPU reference adds in, and for f = 2, 4, 8
+// (f*f a power of two) the result equals it bit for bit.  No fast-math in this build, so the written order is the executed order; no
+// tree, no partial sums per row.  Pure streaming: for f = 4 a lane owns one output and reads four 16-byte rows, for f = 8 two float4 per
+// row, for f = 2 one float4 per row feeds the lane's two outputs; consecutive lanes read consecutive 16-byte words.  The backward
+// stores whole float4s of dx.  The vector kernels need W % 4 == 0 and 16-byte aligned bases (the launchers check); anything else, and
+// every other f, takes the scalar kernels.
+__global__ __launch_bounds__(256) void area_down_fwd_kernel(const float* x, float* y, int planes, int H, int W, int f) {
+  const int OH = H / f, OW = W / f;
+  const long total = (long)planes * OH * OW;
+  const float ff = (float)(f * f);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ox = (int)(i % OW); const long t = i / OW;       // t = plane * OH + oy, and H = OH * f: the window's first row is t * f
+    const float* xp = x + t * f * W + (long)ox * f;
+    float acc = 0.f;
+    for (int a = 0; a < f; ++a)
+      for (int b = 0; b < f; ++b) acc += xp[(long)a * W + b];
+    y[i] = acc / ff;
+  }
+}
+template <int F>      // F = 4, 8: one output per lane; F = 2: two (one float4 per input row)
+__global__ __launch_bounds__(256) void area_down_fwd_vec_kernel(const float* x, float* y, int planes, int H, int W) {
+  constexpr int PER = F == 2 ? 2 : 1;          // outputs per lane
+  constexpr int NV = F * PER / 4;              // float4 per input row per lane
+  const int OH = H / F, OWL = W / (F * PER);   // lanes per output row
+  const long total = (long)planes * OH * OWL;
+  const float ff = (float)(F * F);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int l = (int)(i % OWL); const long t = i / OWL;
+    const float* xp = x + t * F * W + (long)l * (F * PER);
+    float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+    for (int a = 0; a < F; ++a) {
+      float4 v[NV];
+#pragma unroll
+      for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const float4*>(xp + (long)a * W + 4 * q);
+      if (F == 2) {
+        acc0 += v[0].x; acc0 += v[0].y;
+        acc1 += v[0].z; acc1 += v[0].w;
+      } else {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) { acc0 += v[q].x; acc0 += v[q].y; acc0 += v[q].z; acc0 += v[q].w; }
+      }
+    }
+    if (F == 2) *reinterpret_cast<float2*>(y + i * 2) = make_float2(acc0 / ff, acc1 / ff);      // (OW even, y 8-byte aligned)
+    else y[i] = acc0 / ff;
+  }
+}
+__global__ __launch_bounds__(256) void area_down_bwd_kernel(const float* dy, float* dx, int accumulate, int planes, int H, int W, int f) {
+  const int OH = H / f, OW = W / f;
+  const long total = (long)planes * H * W;
+  const float ff = (float)(f * f);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ix = (int)(i % W); const long t = i / W;
+    const int iy = (int)(t % H); const long pl = t / H;
+    const float g = dy[(pl * OH + iy / f) * OW + ix / f] / ff;
+    dx[i] = accumulate ? dx[i] + g : g;
+  }
+}
+template <int F>      // one float4 of dx per lane (W % 4 == 0): F = 4, 8 replicate one dy value, F = 2 two
+__global__ __launch_bounds__(256) void area_down_bwd_vec_kernel(const float* dy, float* dx, int accumulate, int planes, int H, int W) {
+  const int OH = H / F, OW = W / F, W4 = W / 4;
+  const long total = (long)planes * H * W4;
+  const float ff = (float)(F * F);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int q = (int)(i % W4); const long t = i / W4;
+    const int iy = (int)(t % H); const long pl = t / H;
+    const float* gp = dy + (pl * OH + iy / F) * OW + (q * 4) / F;
+    float4 g;
+    if (F == 2) { const float g0 = gp[0] / ff, g1 = gp[1] / ff; g = make_float4(g0, g0, g1, g1); }
+    else { const float g0 = gp[0] / ff; g = make_float4(g0, g0, g0, g0); }
+    float4* o = reinterpret_cast<float4*>(dx) + i;
+    if (accumulate) { const float4 d = *o; g.x += d.x; g.y += d.y; g.z += d.z; g.w += d.w; }
+    *o = g;
+  }
+}
+static inline bool area_vec_ok(const void* big, int W, int f) {      // the full-resolution side: 16-byte rows
+  return (f == 2 || f == 4 || f == 8) && W % 4 == 0 && (reinterpret_cast<uintptr_t>(big) & 15) == 0;
+}
+extern "C" int csbsr_area_down_fwd(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t f, csbsr_stream_t s) {
+  CSBSR_CHECK(x && y && f >= 1 && planes >= 0 && H >= 0 && W >= 0, "area_down_fwd: bad args");
+  CSBSR_CHECK(H % f == 0 && W % f == 0, "area_down_fwd: %d x %d is no multiple of the factor %d", H, W, f);
+  const long outs = (long)planes * (H / f) * (W / f);
+  const bool vec = area_vec_ok(x, W, f) && (f != 2 || (reinterpret_cast<uintptr_t>(y) & 7) == 0);
+  if (vec && f == 2)
+    hipLaunchKernelGGL((area_down_fwd_vec_kernel<2>), dim3(grid_for(outs / 2)), dim3(256), 0, ST(s), x, y, planes, H, W);
+  else if (vec && f == 4)
+    hipLaunchKernelGGL((area_down_fwd_vec_kernel<4>), dim3(grid_for(outs)), dim3(256), 0, ST(s), x, y, planes, H, W);
+  else if (vec)
+    hipLaunchKernelGGL((area_down_fwd_vec_kernel<8>), dim3(grid_for(outs)), dim3(256), 0, ST(s), x, y, planes, H, W);
+  else
+    hipLaunchKernelGGL(area_down_fwd_kernel, dim3(grid_for(outs)), dim3(256), 0, ST(s), x, y, planes, H, W, f);
+  CSBSR_LAUNCH_CHECK("csbsr_area_down_fwd");
+  return 0;
+}
+extern "C" int csbsr_area_down_bwd(const float* dy, float* dx, int32_t accumulate, int32_t planes, int32_t H, int32_t W, int32_t f,
+                                   csbsr_stream_t s) {
+  CSBSR_CHECK(dy && dx && f >= 1 && planes >= 0 && H >= 0 && W >= 0, "area_down_bwd: bad args");
+  CSBSR_CHECK(H % f == 0 && W % f == 0, "area_down_bwd: %d x %d is no multiple of the factor %d", H, W, f);
+  const long ins = (long)planes * H * W;
+  if (!area_vec_ok(dx, W, f))
+    hipLaunchKernelGGL(area_down_bwd_kernel, dim3(grid_for(ins)), dim3(256), 0, ST(s), dy, dx, accumulate, planes, H, W, f);
+  else if (f == 2)
+    hipLaunchKernelGGL((area_down_bwd_vec_kernel<2>), dim3(grid_for(ins / 4)), dim3(256), 0, ST(s), dy, dx, accumulate, planes, H, W);
+  else if (f == 4)
+    hipLaunchKernelGGL((area_down_bwd_vec_kernel<4>), dim3(grid_for(ins / 4)), dim3(256), 0, ST(s), dy, dx, accumulate, planes, H, W);
+  else
+    hipLaunchKernelGGL((area_down_bwd_vec_kernel<8>), dim3(grid_for(ins / 4)), dim3(256), 0, ST(s), dy, dx, accumulate, planes, H, W);
+  CSBSR_LAUNCH_CHECK("csbsr_area_down_bwd");
+  return 0;
+}
+
 // Bicubic up-scale by an integer factor s (a multiple of 4) as torchvision's Resize(BICUBIC) computes it for a float tensor:
 //   antialias = 1: F.interpolate(bicubic, antialias=True) -- Keys' cubic with A = -0.5, the taps [int(c - 1.5), int(c + 2.5)) CUT to the
 //                  image and the remaining weights renormalised (c = (o + 0.5) / s);

@@ -8,19 +8,22 @@ Here the whole minibatch is degraded in three launches on the training stream, a
 (boundary_loss.py:40-67, identical for the main and the auxiliary head) is computed once per batch next to it, so the loader only
 has to deliver HR crops + masks.
 
-Kernels: csbsr_gaussian_kernels (new), csbsr_blur_fwd (stride 1), csbsr_aa_bicubic_down_fwd, csbsr_sdf.  No CPU / torch fallback.
+Kernels: csbsr_gaussian_kernels (new), csbsr_blur_fwd (stride 1), csbsr_aa_bicubic_down_fwd or csbsr_area_down_fwd, csbsr_sdf.  No CPU / torch fallback.
 """
 import math
 
 import torch
 
 from .. import _lib as L
+from ..config.defaults import check_downscale
 from ..engine import _ptr
 
 
 class DeviceDegradation:
     def __init__(self, scale, ksize=21, sigma_range=(0.2, 4.0), theta_range=(0.0, 180.0), isotropic=False, antialias=True, device="cuda:0",
-                 seed=None):
+                 seed=None, interpolation="bicubic"):
+        # FactorResize's mode (SOLVER.DOWNSCALE_INTERPOLATION): "bicubic", or "area" -- the f x f box mean, for which ``antialias`` has no meaning
+        self.interpolation = check_downscale(interpolation)
         L.load()
         self.scale, self.K, self.sigma_range, self.theta_range = int(scale), int(ksize), tuple(sigma_range), tuple(theta_range)
         self.isotropic, self.antialias = bool(isotropic), bool(antialias)
@@ -61,15 +64,23 @@ class DeviceDegradation:
         k = self.kernels(params)
         blurred = torch.empty_like(hr)
         L.call("csbsr_blur_fwd", _ptr(hr), _ptr(k), B, C, H, W, self.K, 1, None, _ptr(blurred), None, 0, self._stream)
-        h, w = H // self.scale, W // self.scale
-        x = torch.empty(B, C, h, w, dtype=torch.float32, device=self.device)
-        L.call("csbsr_aa_bicubic_down_fwd", _ptr(blurred), _ptr(x), B * C, H, W, self.scale, int(self.antialias), self._stream)
+        x = self.downscale(blurred)
         sdf = None
         if mask is not None:
             mask = mask.to(self.device, torch.float32).contiguous()
             if with_sdf:
                 sdf = self.sdf(mask)
         return x, hr, mask, k, sdf
+
+    def downscale(self, img):
+        """FactorResize (transforms.py:505-531) of a contiguous fp32 device batch [B,C,H,W] -> [B,C,H/s,W/s], in ``self.interpolation``."""
+        B, C, H, W = img.shape
+        x = torch.empty(B, C, H // self.scale, W // self.scale, dtype=torch.float32, device=self.device)
+        if self.interpolation == "area":
+            L.call("csbsr_area_down_fwd", _ptr(img), _ptr(x), B * C, H, W, self.scale, self._stream)
+        else:
+            L.call("csbsr_aa_bicubic_down_fwd", _ptr(img), _ptr(x), B * C, H, W, self.scale, int(self.antialias), self._stream)
+        return x
 
     def sdf(self, mask):
         B, _, H, W = mask.shape

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..config.defaults import check_downscale
 from ..engine import _ptr
 from ..multi_tensor import Staging
 from .degrade import DeviceDegradation
@@ -291,12 +292,17 @@ class DeviceTrainLoader:
 
     The mask is ``bytes / 255`` like the reference's (``mask / 255``, data_preprocess.py:44), so a {0, 255} mask becomes {0, 1}.
     ``blur=False`` (crack_dataset.py:55-58): the kernel target is a delta at the centre, the LR image the down-scaled unblurred crop.
+
+    ``interpolation`` is FactorResize's mode (SOLVER.DOWNSCALE_INTERPOLATION; ``from_cfg`` reads it): "bicubic", or "area", the f x f box
+    mean, on both LR paths; ``antialias`` has no meaning with "area".  It changes no draw and no ``state_dict()``.  The model's loss must
+    use the same mode (``model.downscale``): the trainer's loops compare the two before the first step.
     """
 
     def __init__(self, dataset, crop, scale, ksize=21, *, batch_size, num_iterations=None, blur=True, isotropic=False, augmentation=None,
                  vflip_p=0.0, antialias=True, drop_last=False, seed=None, shard=(0, 1), shuffle=True, resized_crop=None,
-                 shard_mode="sample"):
+                 shard_mode="sample", interpolation="bicubic"):
         self.dataset = dataset
+        self.interpolation = check_downscale(interpolation)
         self.h, self.w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
         self.scale, self.K = int(scale), int(ksize)
         if self.h < 1 or self.w < 1 or self.h % self.scale or self.w % self.scale:
@@ -347,7 +353,8 @@ class DeviceTrainLoader:
         if seed is not None:
             self.gen.manual_seed(int(seed))
         self.device = dataset.device
-        self.deg = DeviceDegradation(self.scale, ksize=self.K, isotropic=isotropic, antialias=antialias, device=self.device)
+        self.deg = DeviceDegradation(self.scale, ksize=self.K, isotropic=isotropic, antialias=antialias, device=self.device,
+                                     interpolation=self.interpolation)
         self.deg.gen = self.gen          # one generator for every draw
         self.antialias = bool(antialias)
         self.resize_antialias = True          # of the window's resample: torchvision's default for tensors since 0.17
@@ -359,7 +366,8 @@ class DeviceTrainLoader:
         """Arguments from a reference-style config tree: INPUT.IMAGE_SIZE, MODEL.SCALE_FACTOR, BLUR.*, SOLVER.BATCH_SIZE / MAX_ITER, and
         DATASET.DATA_AUGMENTATION when the tree has that node (it is not in the default tree: the shipped yaml's list then applies)."""
         args = dict(crop=tuple(cfg.INPUT.IMAGE_SIZE), scale=cfg.MODEL.SCALE_FACTOR, ksize=cfg.BLUR.KERNEL_SIZE_OUTPUT,
-                    batch_size=cfg.SOLVER.BATCH_SIZE, num_iterations=cfg.SOLVER.MAX_ITER, blur=cfg.BLUR.FLAG, isotropic=cfg.BLUR.ISOTROPIC)
+                    batch_size=cfg.SOLVER.BATCH_SIZE, num_iterations=cfg.SOLVER.MAX_ITER, blur=cfg.BLUR.FLAG, isotropic=cfg.BLUR.ISOTROPIC,
+                    interpolation=cfg.SOLVER.get("DOWNSCALE_INTERPOLATION", "bicubic"))
         node = cfg.get("DATASET") if hasattr(cfg, "get") else None
         if node is not None and "DATA_AUGMENTATION" in node:
             args["augmentation"] = node["DATA_AUGMENTATION"]
@@ -470,8 +478,7 @@ class DeviceTrainLoader:
                 return (out[0], out[1], out[3]) if self.image_only else out
             k = torch.zeros(B, 1, self.K, self.K, dtype=torch.float32, device=self.device)
             k[:, :, self.K // 2, self.K // 2] = 1.0
-            x = torch.empty(B, 3, self.h // self.scale, self.w // self.scale, dtype=torch.float32, device=self.device)
-            L.call("csbsr_aa_bicubic_down_fwd", _ptr(hr), _ptr(x), B * 3, self.h, self.w, self.scale, int(self.antialias), self.deg._stream)
+            x = self.deg.downscale(hr)
             return (x, hr, k) if self.image_only else (x, hr, mask, k, self.deg.sdf(mask))
 
     def __len__(self):

@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from ..config import path_config
+from ..config.defaults import check_downscale
 from ..engine import Engine, _ptr
 from ..utils.misc import fix_model_state_dict
 from .kbpn import KBPN
@@ -130,7 +131,7 @@ def load_pretrained_sr(model, cfg, root="weights"):
 
 
 class _JointBase(nn.Module):
-    def __init__(self, cfg, antialias=True, device="cuda:0", seed=None, pretrained_root="weights", sr_only=False):
+    def __init__(self, cfg, antialias=True, device="cuda:0", seed=None, pretrained_root="weights", sr_only=False, sr_transforms=None):
         super().__init__()
         # ``sr_only`` (SRModelWithLoss): KBPN and its loss alone -- no detector is constructed, moved to the device or given a gradient bucket
         self.sr_only = bool(sr_only)
@@ -156,6 +157,15 @@ class _JointBase(nn.Module):
                 raise NotImplementedError("only MODEL.JOINT_LEARNING=True with SR_SEG_INV=False (SR feeds the detector, one joint loss) is built")
         self.cfg = cfg
         self.pc = path_config(cfg, antialias)
+        # SOLVER.DOWNSCALE_INTERPOLATION (train.py:43): FactorResize's mode, which the reference hands to the datasets and to KBPNLoss's
+        # Get_pseudo_lr alike; it exits on any other value.  JointModel and MODEL.SR="bicubic" models have no SR loss: the key has no effect
+        # on them, as in the reference.  A ``sr_transforms`` that carries an ``interpolation`` (the reference's FactorResize under
+        # csbsr_amd.dropin: the string 'area' or torchvision's BICUBIC enum) must say the same as the cfg key
+        self.downscale = check_downscale(self.pc.downscale, "SOLVER.DOWNSCALE_INTERPOLATION", NotImplementedError)
+        given = getattr(sr_transforms, "interpolation", None)
+        if given is not None and str(getattr(given, "value", given)).lower() != self.downscale:
+            raise ValueError(f"sr_transforms down-scales with {given!r} but SOLVER.DOWNSCALE_INTERPOLATION={self.downscale!r}: the loss "
+                             "would not model the degradation the data was made with")
         self.scale_factor = cfg.MODEL.SCALE_FACTOR
         self.norm_method = cfg.SOLVER.NORM_SR_OUTPUT
         self.seg_model_name = None if self.sr_only else cfg.MODEL.DETECTOR_TYPE
@@ -403,7 +413,9 @@ class _TrainBase(_JointBase):
 
     def _sr_loss_terms(self, iter, x, hr, kgt, sr32, kvec, seg32, mask):
         """KBPNLoss (sr_loss_functions.py:35-66), forward sums only -> (sr_loss [B], kernel_preds [B,1,K,K], what _sr_loss_seed needs).
-        ``seg32`` / ``mask`` feed the oriented weight map alone; the SR-only model has neither and refuses the keys that would ask for it."""
+        ``seg32`` / ``mask`` feed the oriented weight map alone; the SR-only model has neither and refuses the keys that would ask for it.
+        The pseudo-LR image is the blurred SR image down-scaled as ``pc.downscale`` says (Get_pseudo_lr, sr_loss_functions.py:94): the
+        antialiased bicubic resize or, with "area", the f x f box mean -- ``antialias`` has no meaning then."""
         eng, pc = self._rt["eng"], self.pc
         B, _, h, w = x.shape
         H, W = h * pc.scale, w * pc.scale
@@ -422,7 +434,10 @@ class _TrainBase(_JointBase):
         blurred = eng.f32(B, 3, H, W, zero=False)
         L.call("csbsr_blur_fwd", _ptr(sr32), _ptr(vec), B, 3, H, W, K, 1, None, _ptr(blurred), None, 0, eng.stream)
         lr_pred = eng.f32(B, 3, h, w, zero=False)
-        L.call("csbsr_aa_bicubic_down_fwd", _ptr(blurred), _ptr(lr_pred), B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
+        if pc.downscale == "area":
+            L.call("csbsr_area_down_fwd", _ptr(blurred), _ptr(lr_pred), B * 3, H, W, pc.scale, eng.stream)
+        else:
+            L.call("csbsr_aa_bicubic_down_fwd", _ptr(blurred), _ptr(lr_pred), B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
         s_hr, s_lr = eng.f32(B), eng.f32(B)
         L.call("csbsr_l1_fwd_bwd", _ptr(sr32), _ptr(hr), _ptr(wmap), B, 3, hw, _ptr(s_hr), 0.0, None, None, 0, eng.stream)
         L.call("csbsr_l1_fwd_bwd", _ptr(lr_pred), _ptr(x), _ptr(wmap_lr), B, 3, h * w, _ptr(s_lr), 0.0, None, None, 0, eng.stream)
@@ -555,7 +570,8 @@ class _TrainBase(_JointBase):
 
     def _sr_loss_seed(self, st, dsr_loss, gs, dsr32):
         """Seeds of the KBPN backward from the SR loss: adds dLoss/d sr_preds (x ``gs``) into ``dsr32`` and returns dLoss/d kernel vector
-        [B,kk] (zeros when the caller's scalar did not use the SR loss)."""
+        [B,kk] (zeros when the caller's scalar did not use the SR loss).  The LR term goes back through the adjoint of the down-scale
+        ``pc.downscale`` names; with "area" that is dy / f^2 replicated and ``antialias`` has no meaning."""
         eng, pc = self._rt["eng"], self.pc
         B, h, w = st["B"], st["h"], st["w"]
         H, W = h * pc.scale, w * pc.scale
@@ -573,7 +589,10 @@ class _TrainBase(_JointBase):
             L.call("csbsr_l1_fwd_bwd", _ptr(st["lr_pred"]), _ptr(st["x"]), _ptr(st["wmap_lr"]), B, 3, h * w, None, 1.0, _ptr(g_lr), _ptr(dlr), 0,
                    eng.stream)
             dbl = eng.f32(B, 3, H, W, zero=False)
-            L.call("csbsr_aa_bicubic_down_bwd", _ptr(dlr), _ptr(dbl), 0, B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
+            if pc.downscale == "area":
+                L.call("csbsr_area_down_bwd", _ptr(dlr), _ptr(dbl), 0, B * 3, H, W, pc.scale, eng.stream)
+            else:
+                L.call("csbsr_aa_bicubic_down_bwd", _ptr(dlr), _ptr(dbl), 0, B * 3, H, W, pc.scale, int(pc.antialias), eng.stream)
             L.call("csbsr_blur_bwd_input", _ptr(dbl), _ptr(st["vec"]), _ptr(dsr32), 1, B, 3, H, W, K, 1, eng.stream)
             dvec = eng.f32(B, K * K)
             L.call("csbsr_blur_bwd_kernel", _ptr(dbl), _ptr(st["sr32"]), _ptr(dvec), B, 3, H, W, K, 1, eng.stream)
@@ -646,7 +665,7 @@ class _TrainBase(_JointBase):
 
 class JointModelWithLoss(_TrainBase):
     def __init__(self, cfg, num_train_ds, resume_iter, sr_transforms=None, antialias=True, device="cuda:0", seed=None, pretrained_root="weights"):
-        super().__init__(cfg, antialias, device, seed, pretrained_root)
+        super().__init__(cfg, antialias, device, seed, pretrained_root, sr_transforms=sr_transforms)
         # bicubic: calc_sr_loss returns None before it looks at the loss function (build_model.py:163-166), so the keys that only shape
         # KBPN or the SR loss have no effect, as in the reference (the list: DESIGN.md section 1.5); _JointBase's refusals of values no model
         # of this build takes (SUM_LR_ERROR_POS, NUM_CLASSES, SR_SEG_INV, JOINT_LEARNING) hold for this model too
@@ -765,7 +784,7 @@ class SRModelWithLoss(_TrainBase):
         if cfg.SOLVER.ORIENTED_WEIGHT_ITER != -1 and (cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SR_AMP != 0 or cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0):
             # sr_loss_functions.py hands segment_preds=None to the oriented weight there: the reference fails at the first such iteration
             raise NotImplementedError("an oriented SR-loss weight needs the detector's map, which the SR-only model does not have")
-        super().__init__(cfg, antialias, device, seed, pretrained_root, sr_only=True)
+        super().__init__(cfg, antialias, device, seed, pretrained_root, sr_only=True, sr_transforms=sr_transforms)
         self.sr_loss_fn = "KBPNLoss"
         self._init_loss_scale()
 

@@ -275,9 +275,24 @@ class ValidationAccumulator:
         return out
 
 
+def check_downscale_agrees(model, *loaders):
+    """SOLVER.DOWNSCALE_INTERPOLATION names ONE resize in the reference (train.py:43), used by the datasets and by KBPNLoss's pseudo-LR
+    alike.  Here the loader (``.interpolation``) and the model (``.downscale``) each carry it: a loss that models another degradation
+    than the data was made with trains silently wrong, so a disagreement is a ValueError before the first step.  A loader (or a model)
+    that does not carry the attribute -- any plain iterable of batches -- is not checked."""
+    want = getattr(model, "downscale", None)
+    for loader in loaders:
+        have = getattr(loader, "interpolation", None)
+        if want is not None and have is not None and have != want:
+            raise ValueError(f"the loader down-scales with {have!r} but the model's SR loss with {want!r} (SOLVER.DOWNSCALE_INTERPOLATION): "
+                             "build both from the same cfg")
+
+
 def _validation_pass(model, loader, seed, acc, add_batch):
-    """The skeleton ``validate`` and ``validate_sr`` share: re-seed the loader's generator (``seed`` not None), the model in ``eval()`` under
+    """The skeleton ``validate`` and ``validate_sr`` share: the loader's down-scale checked against the model's (check_downscale_agrees),
+    re-seed the loader's generator (``seed`` not None), the model in ``eval()`` under
     ``no_grad``, ``add_batch(batch)`` for every batch the rank holds rows of, the mode restored, ``acc.result()``."""
+    check_downscale_agrees(model, loader)
     if seed is not None:
         loader.gen.manual_seed(int(seed))
     was_training = model.training
@@ -510,7 +525,8 @@ def _loop(regime, model, optimizer, scheduler, train_loader, eval_loader, resume
 def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *, resume_iter=0, log_step=50, save_step=2000, eval_step=2000,
              output_dir=None, log=print_line, hooks=None, process_group=None):
     """Train over ``train_loader`` (any iterable of ``(x, hr, mask, k)`` or ``(x, hr, mask, k, sdf)``), iterations counted from
-    ``resume_iter + 1``.  Per iteration: set_alpha_phase, model.train(), zero_grad, forward, calc_loss, backward, optimizer.step(),
+    ``resume_iter + 1``.  A loader that carries ``.interpolation`` (DeviceTrainLoader) must down-scale as the model's loss does
+    (``model.downscale``, SOLVER.DOWNSCALE_INTERPOLATION): ValueError before the first step otherwise.  Per iteration: set_alpha_phase, model.train(), zero_grad, forward, calc_loss, backward, optimizer.step(),
     scheduler.step().  ``hooks`` (a dict or an object) may carry ``before_step(iteration, model)``, called first in an iteration, and
     ``after_step(iteration, model, record)``, called last with that iteration's log record or None.
 
@@ -528,6 +544,7 @@ def do_train(cfg, model, optimizer, scheduler, train_loader, eval_loader=None, *
     ``after_step`` receives the record on every rank; ``overflow_steps`` is common already (the ranks agree on the skip).  Validation and
     checkpoints: see ``validate`` and ``save_checkpoint``; both are collectives, and a drifted replica raises ReplicaMismatch on every
     rank before a file is written."""
+    check_downscale_agrees(model, train_loader, eval_loader)
     pg, rank, world = _dist(process_group)
     if pg is not None:
         dev = _device_of(model)
@@ -622,6 +639,8 @@ def do_pretrain_sr(cfg, model, optimizer, scheduler, train_loader, eval_loader=N
     and its result goes to ``log``.  Data-parallel pretraining is not built: NotImplementedError before anything touches the device."""
     if _forced() or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
         raise NotImplementedError("do_pretrain_sr is single-GPU: data-parallel SR pretraining is not built")
+    check_downscale_agrees(model, train_loader, eval_loader)
+
     def losses(iteration, batch):
         x, hr, k = batch
         sr = model(iteration, x, sr_targets=hr, kernel_targets=k.detach())[0].mean()

@@ -489,6 +489,12 @@ int csbsr_aa_bicubic_down_fwd(const float* x, float* y, int32_t planes, int32_t 
                               int32_t antialias, csbsr_stream_t s);
 int csbsr_aa_bicubic_down_bwd(const float* dy, float* dx, int32_t accumulate, int32_t planes, int32_t H, int32_t W,
                               int32_t f, int32_t antialias, csbsr_stream_t s);
+/* FactorResize('area') = F.interpolate(mode='area') by an integer factor f (H % f == W % f == 0, else an error):
+ * y[p,oy,ox] = (sum_{a<f} sum_{b<f} x[p,oy*f+a,ox*f+b]) / (f*f), one fp32 sum with a outer and b inner, then one division -- bit-equal
+ * to the CPU reference at f = 2, 4, 8; dx[p,iy,ix] (+)= dy[p,iy/f,ix/f] / (f*f).  No atomics, no scratch. */
+int csbsr_area_down_fwd(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t f, csbsr_stream_t s);
+int csbsr_area_down_bwd(const float* dy, float* dx, int32_t accumulate, int32_t planes, int32_t H, int32_t W, int32_t f,
+                        csbsr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------- blur kernels */
 /* Per-sample depthwise KxK cross-correlation (kbpn.py:394-402 stride = scale; sr_loss_functions.py:89-94
