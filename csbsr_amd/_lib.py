@@ -155,6 +155,7 @@ SIGNATURES = {
     "csbsr_blur_bwd_input": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_blur_bwd_kernel": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "csbsr_sdf": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "csbsr_crack_weight": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, vp]),
     "csbsr_segloss_reduce": (i32, [vp, vp, vp, i32, i64, vp, f32, f32, vp]),
     "csbsr_segloss_finish": (i32, [vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
     "csbsr_l1_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i64, vp, f32, vp, vp, i32, vp]),

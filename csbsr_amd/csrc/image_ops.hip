@@ -1300,3 +1300,86 @@ extern "C" int csbsr_sdf(const float* mask, float* sdf, float* scratch /*3*N*H*W
   CSBSR_LAUNCH_CHECK("csbsr_sdf");
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------- crack-oriented weight
+// w^C = lambda * exp(-amp * d), d = exact Euclidean distance to the nearest crack pixel (CrackOrientedExpWeight, oriented_weight.py:46-58,
+// 92-119).  Column pass of its own: a pixel is foreground when the mask value TRUNCATED TO uint8 is non-zero (the reference's
+// astype(np.uint8): 0.5 and 0.99 are background; mask values in [0, 256)), not csbsr_sdf's ``!= 0``; g = vertical distance to the nearest
+// foreground pixel of the column, 1e9 when the column has none.
+__global__ void crack_cols_kernel(const float* mask, float* g, int N, int H, int W) {
+  const long total = (long)N * W;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W); const long n = i / W;
+    const float* mp = mask + n * H * W + x;
+    float* gp = g + n * H * W + x;
+    const float BIG = 1e9f;
+    float d = BIG;
+    for (int y = 0; y < H; ++y) {
+      const bool fg = (unsigned char)(int)mp[(long)y * W] != 0;
+      d = fg ? 0.f : d + 1.f;
+      gp[(long)y * W] = d;
+    }
+    d = BIG;
+    for (int y = H - 1; y >= 0; --y) {
+      const bool fg = (unsigned char)(int)mp[(long)y * W] != 0;
+      d = fg ? 0.f : d + 1.f;
+      const float cur = gp[(long)y * W];
+      gp[(long)y * W] = cur < d ? cur : d;
+    }
+  }
+}
+// Row pass: edt_rows_kernel's exact block-bounded search (squares in LDS, 32-column block minima as lower bounds) with the weight as its
+// epilogue -- the distance goes from the register into expf and only w is written.  A row whose every column is 1e9 belongs to a sample
+// without a foreground pixel (each g column spans the whole image): the reference leaves that sample's distance map at zero, w = lambda.
+__global__ __launch_bounds__(256) void crack_rows_weight_kernel(const float* g, float* w, int W, float namp, float lambda) {
+  extern __shared__ float srow[];      // [W] squares, then [nb] block minima
+  const long row = blockIdx.x;         // n*H + y
+  const float* gp = g + row * W;
+  const int nb = (W + 31) >> 5;
+  float* bmin = srow + W;
+  for (int x = threadIdx.x; x < W; x += 256) { const float v = gp[x]; srow[x] = v >= 1e8f ? 1e18f : v * v; }
+  __syncthreads();
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    float m = 1e18f;
+    const int x1 = min(W, 32 * b + 32);
+    for (int x = 32 * b; x < x1; ++x) m = fminf(m, srow[x]);
+    bmin[b] = m;
+  }
+  __syncthreads();
+  for (int x = threadIdx.x; x < W; x += 256) {
+    float best = srow[x];
+    const int bx = x >> 5;
+    auto scan = [&](int b) {
+      const int x1 = min(W, 32 * b + 32);
+      for (int xx = 32 * b; xx < x1; ++xx) {
+        const float d = (float)(x - xx);
+        best = fminf(best, srow[xx] + d * d);
+      }
+    };
+    if (bmin[bx] < best) scan(bx);
+    for (int d = 1; d < nb; ++d) {
+      const int bl = bx - d, br = bx + d;
+      const float gl = (float)(x - (32 * bl + 31)), gr = (float)(32 * br - x);      // gap to the nearest column of the block (>= 1)
+      const bool lin = bl >= 0 && gl * gl < best, rin = br < nb && gr * gr < best;
+      if (!lin && !rin) break;      // both sides out of range or out of reach: the gaps only grow and ``best`` only shrinks
+      if (lin && bmin[bl] + gl * gl < best) scan(bl);
+      if (rin && bmin[br] + gr * gr < best) scan(br);
+    }
+    w[row * W + x] = best >= 1e17f ? lambda : lambda * expf(namp * sqrtf(best));
+  }
+}
+extern "C" int csbsr_crack_weight(const float* mask, float* w_hr, float* w_lr, float* scratch /*N*H*W floats*/, int32_t N, int32_t H, int32_t W,
+                                  float amp, float lambda, int32_t scale, csbsr_stream_t s) {
+  CSBSR_CHECK(mask && w_hr && scratch, "crack_weight: null");
+  CSBSR_CHECK(N > 0 && H > 0 && W > 0, "crack_weight: empty batch");
+  CSBSR_CHECK(W <= 8192, "crack_weight: row longer than 8192 not supported");
+  CSBSR_CHECK(!w_lr || (scale >= 1 && H % scale == 0 && W % scale == 0), "crack_weight: the LR map needs H and W divisible by the scale");
+  hipStream_t st = ST(s);
+  hipLaunchKernelGGL(crack_cols_kernel, dim3(grid_for((long)N * W, 64)), dim3(64), 0, st, mask, scratch, N, H, W);
+  hipLaunchKernelGGL(crack_rows_weight_kernel, dim3(N * H), dim3(256), (W + (W + 31) / 32) * sizeof(float), st, scratch, w_hr, W, -amp, lambda);
+  if (w_lr)      // F.interpolate(w_hr, scale_factor=1/scale, mode="bilinear"): the launch of csbsr_bilinear32_fwd (align_corners False)
+    hipLaunchKernelGGL(bilinear32_fwd_kernel, dim3(grid_for((long)N * (H / scale) * (W / scale))), dim3(256), 0, st, w_hr, w_lr, N, H, W,
+                       H / scale, W / scale, 0);
+  CSBSR_LAUNCH_CHECK("csbsr_crack_weight");
+  return 0;
+}

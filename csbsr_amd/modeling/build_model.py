@@ -424,13 +424,16 @@ class _TrainBase(_JointBase):
         ksum = kvec.sum(1, keepdim=True)
         vec = (kvec / ksum).contiguous()
         K = pc.ksize_out
+        oriented = iter > pc.oriented_w_iter and pc.oriented_w_iter != -1
         wmap = None
-        if iter > pc.oriented_w_iter and pc.oriented_w_iter != -1 and pc.sfo_sr_amp != 0:
+        if oriented and pc.sfo_sr_amp != 0:
             wmap = torch.exp(pc.sfo_sr_amp * (seg32 - mask).abs()).contiguous()      # oriented_weight.py:73-83 (detached)
         wmap_lr = None
         if wmap is not None:
             wmap_lr = eng.f32(B, 1, h, w, zero=False)
             L.call("csbsr_bilinear32_fwd", _ptr(wmap), _ptr(wmap_lr), B, H, W, h, w, 0, eng.stream)
+        if oriented and pc.co_sr_amp != 0:
+            wmap, wmap_lr = self._crack_weight(mask, wmap, wmap_lr)
         blurred = eng.f32(B, 3, H, W, zero=False)
         L.call("csbsr_blur_fwd", _ptr(sr32), _ptr(vec), B, 3, H, W, K, 1, None, _ptr(blurred), None, 0, eng.stream)
         lr_pred = eng.f32(B, 3, h, w, zero=False)
@@ -449,6 +452,21 @@ class _TrainBase(_JointBase):
         sr_loss = sr_w[0] * s_hr / (3 * hw) + sr_w[1] * s_lr / (3 * h * w) + sr_w[2] * k_l
         del blurred
         return sr_loss, kpred, dict(ksum=ksum, vec=vec, lr_pred=lr_pred, wmap=wmap, wmap_lr=wmap_lr, sr_w=sr_w)
+
+    def _crack_weight(self, mask, wf, wf_lr):
+        """SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP: the crack-oriented weight w^C = 2 exp(-amp d) of the whole batch (CrackOrientedExpWeight,
+        oriented_weight.py:46-58,92-119; d = distance to the nearest crack pixel, a pixel being a crack where the mask truncated to uint8
+        is non-zero; 2 everywhere for a sample without one) and its bilinear LR reduction -> (HR weight, LR weight) of the two L1 terms,
+        times the fail-oriented pair ``wf`` / ``wf_lr`` where that is on: KBPNLoss.multiple_weight's order, the LR weight being the product
+        of the two reduced maps.  Constants of the backward.  lambda is the class default 2; the reference's constructor also reads
+        CRACK_ORIENTED_WEIGHT4SR_BIAS and never uses it, so this build has no such key."""
+        eng, pc = self._rt["eng"], self.pc
+        B, _, H, W = mask.shape
+        wc, wc_lr = eng.f32(B, 1, H, W, zero=False), eng.f32(B, 1, H // pc.scale, W // pc.scale, zero=False)
+        scratch = eng.f32(B * H * W, zero=False)
+        L.call("csbsr_crack_weight", _ptr(mask), _ptr(wc), _ptr(wc_lr), _ptr(scratch), B, H, W, pc.co_sr_amp, 2.0, pc.scale, eng.stream)
+        del scratch
+        return (wc, wc_lr) if wf is None else (wc * wf, wc_lr * wf_lr)
 
     def _auto_resident(self, B, mb, H, W, agree=True):
         """micro-batches whose KBPN activations fit next to the detector's working set -- the SR-only model has none, so its budget has
@@ -671,8 +689,12 @@ class JointModelWithLoss(_TrainBase):
         # of this build takes (SUM_LR_ERROR_POS, NUM_CLASSES, SR_SEG_INV, JOINT_LEARNING) hold for this model too
         if cfg.SOLVER.SEG_LOSS_FUNC != "BoundaryCombo" or (cfg.SOLVER.SR_LOSS_FUNC != "KBPN" and not self.bicubic):
             raise NotImplementedError("csbsr_amd builds SEG_LOSS_FUNC=BoundaryCombo with SR_LOSS_FUNC=KBPN")
-        if cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SS_AMP != 0 or cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0 or cfg.SOLVER.INTERM_SSLOSSWEGHT4SR:
-            raise NotImplementedError("oriented loss weights other than SEG_FAIL_ORIENTED_WEIGHT4SR are not built")
+        if cfg.SOLVER.SEG_FAIL_ORIENTED_WEIGHT4SS_AMP != 0 or cfg.SOLVER.INTERM_SSLOSSWEGHT4SR:
+            raise NotImplementedError("oriented loss weights other than SEG_FAIL_ORIENTED_WEIGHT4SR and CRACK_ORIENTED_WEIGHT4SR are not built")
+        if cfg.SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP != 0 and cfg.SOLVER.ORIENTED_WEIGHT_ITER == -1:
+            raise NotImplementedError("SOLVER.CRACK_ORIENTED_WEIGHT4SR_AMP with ORIENTED_WEIGHT_ITER = -1: KBPNLoss applies no oriented weight "
+                                      "then, so the key could never act, and this build keeps refusing the combination (tests/test_host_cpu.py pins "
+                                      "it); set ORIENTED_WEIGHT_ITER to the iteration after which the weight applies")
         seg_rsm = resume_iter - (cfg.SOLVER.SR_PRETRAIN_ITER[1] - 1) if resume_iter > (cfg.SOLVER.SR_PRETRAIN_ITER[1] - 1) else 0
         per_epoch = num_train_ds // cfg.SOLVER.BATCH_SIZE + 1
         self.ss_loss_fn = BoundaryComboState(per_epoch, seg_rsm, decrease_ratio=cfg.SOLVER.BOUNDARY_DEC_RATIO)

@@ -510,6 +510,14 @@ int csbsr_blur_bwd_kernel(const float* dy, const float* x, float* dk, int32_t N,
 /* Exact Euclidean distance transform + normalised signed distance map of compute_sdf1_1
  * (boundary_loss.py:40-67): mask fp32 [N][H][W] in {0,1} -> sdf.  scratch: 3*N*H*W + 2*N floats. */
 int csbsr_sdf(const float* mask, float* sdf, float* scratch, int32_t N, int32_t H, int32_t W, csbsr_stream_t s);
+/* Crack-oriented SR-loss weight of CrackOrientedExpWeight (oriented_weight.py:46-58,92-119): mask fp32 [N][H][W] ->
+ * w_hr[N][H][W] = lambda * expf(-amp * d), d = exact Euclidean distance to the nearest foreground pixel (0 on
+ * foreground; exact while H*H + W*W < 2^24).  Foreground = the mask value truncated to uint8 is non-zero (values in
+ * [0, 256); 0.99 is background).  A sample without a foreground pixel gets lambda everywhere.  w_lr (may be NULL):
+ * [N][H/scale][W/scale] = F.interpolate(w_hr, scale_factor=1/scale, mode="bilinear"), H and W divisible by scale.
+ * scratch: N*H*W floats.  W <= 8192.  No atomics: bit-reproducible. */
+int csbsr_crack_weight(const float* mask, float* w_hr, float* w_lr, float* scratch, int32_t N, int32_t H, int32_t W,
+                       float amp, float lambda, int32_t scale, csbsr_stream_t s);
 /* BoundaryComboLoss = alpha*(lw0*WBCE + lw1*Dice)/(lw0+lw1) + (1-alpha)*mean(p*sdf)
  * (loss_functions.py:49-75,189-210,258-345; boundary_loss.py:26-38) on probability maps fp32 [N][HW]:
  * reduce -> sums[N][8];  finish -> loss[n] += weight*L, dp (+)= gscale[n]*weight*dL/dp */
