@@ -2,7 +2,9 @@
 (model/engine/inference.py:76-119) for one batch of test images -- patches through JointModel, stitch, clip, PSNR / SSIM of the SR
 image, PSNR of the kernel, and the IoU of the segmentation map at every threshold 0.01 .. 0.99 -- without the [B,99,H,W] broadcast
 tensor and the host numpy reductions.  ``evaluate_dataset`` runs it over a whole HBM-resident test set (csbsr_amd/data/resident_test.py) and
-returns the reference's final report, with the saved images and masks leaving the device as uint8 (csrc/eval_io.hip).
+returns the reference's final report, with the saved images and masks leaving the device as uint8 (csrc/eval_io.hip); on request
+(``pr_tolerance``) also the tolerance-matched precision / recall / F of the map over the same thresholds (csrc/pr_sweep.hip), which the
+reference does not compute.
 ``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
 of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device."""
 import csv
@@ -14,7 +16,7 @@ import torch
 from . import _lib as L
 from .data.patch_sampler import JointPatch
 from .engine import _ptr
-from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep
+from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep, pr_sweep, pr_tol2
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -30,11 +32,14 @@ def _kernel_for_psnr(model, kernel_preds, kernel_targets):
 
 @torch.no_grad()
 def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, masks, kernel_targets, ksize, thresholds=THRESHOLDS,
-                   surface_distance=False):
+                   surface_distance=False, pr_tolerance=None):
     """imgs [B, nPatch, 3, h, w] LR patches (as CrackDataSetTest delivers them), kernel_targets [B, nPatch, K, K];
     returns dict(sr_preds, segment_preds, psnr [B], ssim [B], kernel_psnr [B*nPatch], iou [B, T]) -- numpy arrays for the metrics.
     surface_distance=True adds hd [B, T], msd [B, T] (float64) and the counters hd_outliers, msd_outliers of calc_distance_metrics
-    (inference.py:293-336) at the same thresholds."""
+    (inference.py:293-336) at the same thresholds.  pr_tolerance = a radius in pixels adds pr_counts [B, 4, T] (int64), the tolerance-matched
+    precision / recall counts of ``pr_sweep`` (scores: ``pr_scores``, ``summarize_pr``); None adds nothing."""
+    if pr_tolerance is not None:
+        pr_tol2(pr_tolerance)
     joint = JointPatch()
     imgs = imgs.view(-1, *imgs.shape[2:])
     kernel_targets = kernel_targets.view(-1, 1, *kernel_targets.shape[2:])
@@ -51,6 +56,8 @@ def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, 
                kernel_psnr=kps.cpu().numpy(), iou=iou.cpu().numpy())
     if surface_distance:
         out.update(surface_distance_sweep(segment_preds, masks, thresholds))
+    if pr_tolerance is not None:
+        out["pr_counts"] = pr_sweep(segment_preds, masks, thresholds, pr_tolerance).cpu().numpy().astype(np.int64)
     return out
 
 
@@ -164,6 +171,48 @@ def classification_scores(counts):
     return acc, sens, spec
 
 
+# ------------------------------------------------------------------------------------------------ precision / recall / F
+def pr_scores(counts):
+    """(precision, recall, f) float64 [N, T] from the integer counts [N, 4, T] = (n_pred, tp_pred, tp_gt, n_gt) of ``pr_sweep``:
+    precision = tp_pred / n_pred, recall = tp_gt / n_gt, f = 2 P R / (P + R).  Fixed conventions for the degenerate cells: nothing predicted
+    (n_pred = 0) -> precision 1; no ground truth (n_gt = 0) -> recall 1; P + R = 0 -> f 0."""
+    c = np.asarray(counts, dtype=np.int64)
+    assert c.ndim == 3 and c.shape[1] == 4, f"counts are [N, 4, T], got {c.shape}"
+    n_pred, tp_pred, tp_gt, n_gt = (c[:, i].astype(np.float64) for i in range(4))
+    p = np.where(n_pred > 0, tp_pred / np.maximum(n_pred, 1.0), 1.0)
+    r = np.where(n_gt > 0, tp_gt / np.maximum(n_gt, 1.0), 1.0)
+    f = np.where(p + r > 0, 2.0 * p * r / np.where(p + r > 0, p + r, 1.0), 0.0)
+    return p, r, f
+
+
+def summarize_pr(counts, thresholds):
+    """The summaries the crack / edge-detection literature reports, from the counts [N, 4, T] of ``pr_sweep`` (scores by ``pr_scores``):
+    ODS (optimal dataset scale) = max over thresholds of the F of the counts summed over the images, reached at ODS_threshold (the first
+    such threshold) with P_at_ODS, R_at_ODS; OIS (optimal image scale) = the mean over images of each image's best F; AP = the area under
+    the dataset precision-over-recall curve, by the trapezoid rule across the T points as they are (no extrapolation to recall 0 or 1).
+    The dataset recall never grows with the threshold index, so every trapezoid has a non-negative width."""
+    c = np.asarray(counts, dtype=np.int64)
+    assert c.ndim == 3 and c.shape[1] == 4 and c.shape[2] == len(thresholds) and c.shape[0] >= 1
+    p, r, f = (a[0] for a in pr_scores(c.sum(axis=0, keepdims=True)))
+    j = int(np.argmax(f))
+    ap = float(np.sum((r[:-1] - r[1:]) * (p[:-1] + p[1:]) * 0.5))
+    return {"ODS": float(f[j]), "ODS_threshold": float(thresholds[j]), "OIS": float(np.mean(np.max(pr_scores(c)[2], axis=1))), "AP": ap,
+            "P_at_ODS": float(p[j]), "R_at_ODS": float(r[j])}
+
+
+def write_pr_log(path, counts, thresholds, fnames):
+    """pr_log.csv: per image three rows (P, R, F) of ``pr_scores``, one column per threshold; the header row starts with two empty cells
+    (the image and the score columns).  Values are written with repr, the shortest text that reads back to the same fp64."""
+    scores = pr_scores(counts)
+    assert scores[0].shape == (len(fnames), len(thresholds))
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["", ""] + [repr(float(t)) for t in thresholds])
+        for i, name in enumerate(fnames):
+            for tag, a in zip("PRF", scores):
+                w.writerow([name, tag] + [repr(float(v)) for v in a[i]])
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -225,7 +274,8 @@ class _Saver:
 
 
 @torch.no_grad()
-def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_distance=False, classification=False, save_dir=None):
+def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_distance=False, classification=False, save_dir=None,
+                     pr_tolerance=None):
     """``inference_for_ss`` (model/engine/inference.py:25-207) over a ``DeviceTestLoader``: per batch the computation of ``evaluate_batch``
     -- with the stitch, the clip and the 8-bit quantisation in one kernel (csbsr_stitch_clip_u8) instead of JointPatch's copy and two masked
     assignments -- accumulated into the reference's final report.  ``model`` is any callable with JointModel's evaluation signature.
@@ -233,20 +283,25 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
     Returns dict(fnames, psnr [N], ssim [N], kernel_psnr [N * nPatch], iou [N, T] (fp32, as evaluate_batch returns them), summary);
     ``surface_distance`` adds hd, msd [N, T] float64 and the counters hd_outliers, msd_outliers summed over the batches;
     ``classification`` adds acc, sens, spec [N] float64 at threshold index 49 (integer counts on the device, one fp64 division on the
-    host).  ``summary`` is ``summarize`` of those arrays.
+    host).  ``summary`` is ``summarize`` of those arrays.  ``pr_tolerance`` = a radius in pixels adds pr_counts [N, 4, T] int64 -- per image
+    and threshold (n_pred, tp_pred, tp_gt, n_gt) of ``pr_sweep``: a predicted pixel counts when a ground-truth pixel lies within the
+    radius, and the other way round -- and the keys of ``summarize_pr`` (ODS, ODS_threshold, OIS, AP, P_at_ODS, R_at_ODS) to ``summary``;
+    None (the default) adds nothing.
 
     ``save_dir`` writes what ``test.py --sf_save_image`` writes: images/<fname>, masks/th_<t:.2f>/<fname> for the threshold indices
     [0, 9, 19, ..., 89, 98], masks/th_-1.00/<fname> for the raw map, kernels/<stem>_<j>.png, kernels_origin/<stem>_<j>_origin.png, and
-    iou_log.csv.  Images and masks leave the device as uint8 (csbsr_stitch_clip_u8, csbsr_threshold_planes_u8) through pinned slots with
-    non-blocking copies; PIL encodes batch k while the device runs batch k + 1, and the host waits on a slot's event only.  Without
+    iou_log.csv (and, with ``pr_tolerance``, pr_log.csv next to it: ``write_pr_log``).  Images and masks leave the device as uint8
+    (csbsr_stitch_clip_u8, csbsr_threshold_planes_u8) through pinned slots with non-blocking copies; PIL encodes batch k while the device runs batch k + 1, and the host waits on a slot's event only.  Without
     ``save_dir`` the metrics stay on the device until the last batch has been enqueued (the surface distances, whose second half is host
     work, excepted)."""
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     if classification and len(thresholds) <= CLASSIFICATION_IDX:
         raise ValueError(f"classification metrics are taken at threshold index {CLASSIFICATION_IDX}: {len(thresholds)} thresholds given")
+    if pr_tolerance is not None:
+        pr_tol2(pr_tolerance)                                # a bad radius is refused before anything runs
     saver = _Saver(save_dir, thresholds) if save_dir is not None else None
     save_th = None
-    fnames, acc = [], {k: [] for k in ("psnr", "ssim", "kernel_psnr", "iou", "counts", "hd", "msd")}
+    fnames, acc = [], {k: [] for k in ("psnr", "ssim", "kernel_psnr", "iou", "counts", "hd", "msd", "pr")}
     hd_out = msd_out = 0
     for imgs, sr_targets, masks, kernel_targets, names, img_shape, seg_shape in loader:
         fnames += list(names)
@@ -265,6 +320,8 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
         acc["iou"].append(iou_sweep(segment_preds, masks, thresholds))
         if classification:
             acc["counts"].append(classification_counts(segment_preds, masks, th32[CLASSIFICATION_IDX].to(segment_preds.device)))
+        if pr_tolerance is not None:
+            acc["pr"].append(pr_sweep(segment_preds, masks, thresholds, pr_tolerance))
         if saver is not None:
             if save_th is None:
                 save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(segment_preds.device)
@@ -289,8 +346,13 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
     if classification:
         out["acc"], out["sens"], out["spec"] = classification_scores(torch.cat(acc["counts"]).cpu().numpy())
     out["summary"] = summarize(out["psnr"], out["ssim"], out["kernel_psnr"], out["iou"], out.get("hd"), out.get("msd"))
+    if pr_tolerance is not None:
+        out["pr_counts"] = torch.cat(acc["pr"]).cpu().numpy().astype(np.int64)
+        out["summary"].update(summarize_pr(out["pr_counts"], thresholds))
     if save_dir is not None:
         write_iou_log(os.path.join(save_dir, "iou_log.csv"), out["iou"], thresholds, fnames)
+        if pr_tolerance is not None:
+            write_pr_log(os.path.join(save_dir, "pr_log.csv"), out["pr_counts"], thresholds, fnames)
     return out
 
 

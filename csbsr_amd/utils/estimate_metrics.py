@@ -66,6 +66,41 @@ def iou_sweep(segment_preds, masks, thresholds, smooth=1e-5):
     return out
 
 
+PR_MAX_TOLERANCE = 16.0
+
+
+def pr_tol2(tolerance):
+    """squared radius of the matching disk: floor(tolerance^2) for a radius of 0 .. 16 pixels (2.0 -> 4); anything else is a ValueError."""
+    t = float(tolerance)
+    if not 0.0 <= t <= PR_MAX_TOLERANCE:              # NaN fails both comparisons
+        raise ValueError(f"the matching tolerance is a radius of 0 .. {PR_MAX_TOLERANCE:g} pixels, got {tolerance!r}")
+    return int(np.floor(t * t))
+
+
+def pr_sweep(segment_preds, masks, thresholds, tolerance=2.0):
+    """Tolerance-matched precision / recall counts of (segment_preds - t > 0) vs (masks > 0.5) for every threshold: int32 device tensor
+    [B, 4, len(thresholds)] = (n_pred, tp_pred, tp_gt, n_gt).  A predicted pixel is a true positive when a ground-truth pixel lies within
+    ``tolerance`` pixels of it (tp_pred, for the precision), a ground-truth pixel when a predicted pixel does (tp_gt, for the recall);
+    distances are compared as integers, d^2 <= floor(tolerance^2), and tolerance 0 is pixel-wise matching (csrc/pr_sweep.hip)."""
+    tol2 = pr_tol2(tolerance)
+    L.load()
+    p = _dev32(segment_preds)
+    m = _dev32(masks, p)
+    H, W = int(p.shape[-2]), int(p.shape[-1])
+    p, m = p.reshape(-1, H, W), m.reshape(-1, H, W)
+    B = p.shape[0]
+    assert m.shape[0] == B, "one mask per prediction map"
+    th = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)          # == torch.Tensor(thresholds): fp32 roundings
+    assert bool((th[1:] > th[:-1]).all()), "thresholds must ascend"
+    th = th.to(p.device)
+    T = th.numel()
+    hist = torch.zeros(B, 3, T + 1, dtype=torch.int32, device=p.device)
+    out = torch.empty(B, 4, T, dtype=torch.int32, device=p.device)
+    with torch.cuda.device(p.device):
+        L.call("csbsr_pr_sweep", _ptr(p), _ptr(m), _ptr(th), B, H, W, T, tol2, _ptr(hist), _ptr(out), L.stream(p.device))
+    return out
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

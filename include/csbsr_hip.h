@@ -621,6 +621,18 @@ int csbsr_surface_gather(const uint8_t* lvl, const uint8_t* gt, const int32_t* d
                          int32_t nj, uint16_t* gcol, const int32_t* tab_off, const int32_t* tab_cap, int32_t* tab_keys, uint32_t* tab_cnt,
                          int32_t max_cap, int32_t* rows, int32_t max_rows, int32_t* meta, csbsr_stream_t s);
 
+/* Tolerance-matched precision / recall counts of pred_j = (pred - t_j > 0) against gt = (mask > 0.5) for T ascending thresholds, 1 <= T <= 255,
+ * in one pass (csrc/pr_sweep.hip).  level(p) = the number of thresholds with pred(p) - t_j > 0 in fp32 (the predicate and the
+ * binary search of csbsr_iou_sweep; NaN -> 0); outside the image level = 0 and gt = 0.  With the disk D = {(dy, dx): dy^2 + dx^2 <= tol2},
+ * 0 <= tol2 <= 256, near(p) = any gt pixel in p + D and m(p) = max level in p + D:
+ *   counts[n][0][j] = n_pred  = #{level > j}              counts[n][1][j] = tp_pred = #{level > j and near}
+ *   counts[n][2][j] = tp_gt   = #{gt and m > j}            counts[n][3][j] = n_gt    = #gt (the same for every j)
+ * so precision_j = tp_pred / n_pred and recall_j = tp_gt / n_gt; tol2 = 0 is plain pixel-wise matching (tp_pred = tp_gt = the intersection).
+ * pred, mask fp32 [N][H][W], 1 <= H, W <= 8192 (every count fits an int32), N <= 65535; thresholds fp32 [T] device memory;
+ * hist = caller-zeroed uint32 [N][3][T+1] workspace; counts int32 [N][4][T].  Integer atomics only: results are run-to-run identical. */
+int csbsr_pr_sweep(const float* pred, const float* mask, const float* thresholds, int32_t N, int32_t H, int32_t W, int32_t T, int32_t tol2,
+                   uint32_t* hist, int32_t* counts, csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
