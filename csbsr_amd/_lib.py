@@ -126,12 +126,15 @@ SIGNATURES = {
     "csbsr_conv_thin_dact_eligible": (i32, [vp]),
     "csbsr_conv_split_fused_eligible": (i32, [C.POINTER(ConvDesc)]),
     "csbsr_thin_tp_backward": (i32, [vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp]),
+    "csbsr_conv_pair1x1_slabs": (i32, [i32, i32, i32, vp]),
+    "csbsr_conv_pair1x1_backward": (i32, [vp, i64, i64, i64, vp, i64, i64, i64, vp, f32, i32, i32, i32, vp, i64, i64, i64, vp, vp]),
     "csbsr_round_weights": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "csbsr_dc_bias": (i32, [vp, i32, i32, vp, i64, i32, vp, i64, i32, vp, i32, vp, vp]),
     "csbsr_instnorm_bwd": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i64, vp, vp]),
     "csbsr_border_class_fill": (i32, [vp, vp, i64, i32, i32, i32, i32, vp]),
     "csbsr_border_class_fill_masked": (i32, [vp, vp, i64, vp, i64, C.c_float, i32, i32, i32, i32, vp]),
     "csbsr_border_class_sums": (i32, [vp, i64, vp, i32, i32, i32, i32, vp]),
+    "csbsr_border_class_fill_masked_sums": (i32, [vp, vp, i64, vp, i64, C.c_float, vp, i32, i32, i32, i32, vp]),
     "csbsr_border_class_sums_prelu": (i32, [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),
     "csbsr_ring_class_sums": (i32, [vp, i64, vp, i32, i32, i32, i32, vp]),
     "csbsr_bn_finalize": (i32, [vp, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp]),

@@ -1908,6 +1908,12 @@ __global__ void bcs_fixup_kernel(float* sums, int N, int c) {
   for (int k = 1; k < 16; ++k) border += s_[(long)k * c];
   s_[0] -= border;
 }
+// stages (2) and (3) of the fast path below: the border pixels binned per class, then interior = total - border (the totals are in class 0)
+static void bcs_border_classes(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c, float* epart, csbsr_stream_t s) {
+  hipLaunchKernelGGL(bcs_edges_kernel, dim3(N * 4 * ((c / 8 + 31) / 32) * BCS_SEG), dim3(256), 0, ST(s), (const half_t*)x, (long)ld, epart, H, W, c / 8);
+  hipLaunchKernelGGL(bcs_edges_finish_kernel, dim3((N * 12 * c + 255) / 256), dim3(256), 0, ST(s), (const float*)epart, sums, N, c);
+  hipLaunchKernelGGL(bcs_fixup_kernel, dim3((N * c + 255) / 256), dim3(256), 0, ST(s), sums, N, c);
+}
 static int border_class_sums_impl(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c, const void* t, int64_t t_ld,
                                   float* negdot, csbsr_stream_t s) {
   CSBSR_CHECK(x && sums && c % 8 == 0, "border_class_sums: bad args");
@@ -1931,10 +1937,7 @@ static int border_class_sums_impl(const void* x, int64_t ld, float* sums, int32_
                          (const half_t*)nullptr, 0l, (float*)nullptr);
     }
     if (csbsr_sum_partials_batched(part, chunks, c, c, sums, N, 16l * c, ST(s))) return 1;
-    float* epart = part + n_tot;
-    hipLaunchKernelGGL(bcs_edges_kernel, dim3(N * 4 * ((c / 8 + 31) / 32) * BCS_SEG), dim3(256), 0, ST(s), (const half_t*)x, (long)ld, epart, H, W, c / 8);
-    hipLaunchKernelGGL(bcs_edges_finish_kernel, dim3((N * 12 * c + 255) / 256), dim3(256), 0, ST(s), (const float*)epart, sums, N, c);
-    hipLaunchKernelGGL(bcs_fixup_kernel, dim3((N * c + 255) / 256), dim3(256), 0, ST(s), sums, N, c);
+    bcs_border_classes(x, ld, sums, N, H, W, c, part + n_tot, s);
     CSBSR_LAUNCH_CHECK("csbsr_border_class_sums");
     return 0;
   }
@@ -1944,6 +1947,73 @@ static int border_class_sums_impl(const void* x, int64_t ld, float* sums, int32_
 }
 extern "C" int csbsr_border_class_sums(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c, csbsr_stream_t s) {
   return border_class_sums_impl(x, ld, sums, N, H, W, c, nullptr, 0, nullptr, s);
+}
+
+// csbsr_border_class_fill_masked and csbsr_border_class_sums OF THE MASK MAP in one pass: the fill streams the mask anyway, so its plain
+// totals ride along -- bcs_total_kernel's walk (same chunks, same lane order, same partial rows: the sums are bit-identical to the
+// stand-alone pass) with the fill's store for every pixel it visits.  The weight gradient of a 3x3 layer behind a global average pool
+// (dPre spatially constant) needs exactly these sums of the layer's input (csbsr_amd/modeling/kp_bwd.py, fold_const_wgrad).
+__global__ __launch_bounds__(256) void bcs_fill_total_kernel(const float* V, half_t* out, long ld, const half_t* mask, long mld, float mslope, int H, int W,
+                                                             int c8, int chunks, float* part) {
+  __shared__ float sred[256][8];
+  const long hw = (long)H * W;
+  const int n = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+  const int cpb = c8 < 256 ? c8 : 256, ppb = 256 / cpb;
+  const int ch = threadIdx.x % cpb, pl = threadIdx.x / cpb;
+  const long per = (hw + chunks - 1) / chunks;
+  const long beg = chunk * per, end = beg + per < hw ? beg + per : hw;
+  for (int cbase = 0; cbase < c8; cbase += cpb) {
+    const int cc = cbase + ch;
+    float a[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = 0.f;
+    if (cc < c8 && pl < ppb)
+      for (long px = beg + pl; px < end; px += ppb) {
+        const h8 m = *reinterpret_cast<const h8*>(mask + ((long)n * hw + px) * mld + cc * 8);
+        const int y = (int)(px / W), x = (int)(px - (long)y * W);
+        const int cls = (y == 0) * 8 + (y == H - 1) * 4 + (x == 0) * 2 + (x == W - 1);
+        const float* v = V + ((long)n * 16 + cls) * c8 * 8 + cc * 8;
+        h8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          a[e] += (float)m[e];
+          o[e] = (half_t)(v[e] * ((float)m[e] > 0.f ? 1.f : mslope));
+        }
+        *reinterpret_cast<h8*>(out + ((long)n * hw + px) * ld + cc * 8) = o;
+      }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sred[threadIdx.x][e] = a[e];
+    __syncthreads();
+    if (threadIdx.x < cpb && cbase + threadIdx.x < c8) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float s_ = 0.f;
+        for (int q = 0; q < ppb; ++q) s_ += sred[q * cpb + threadIdx.x][e];
+        part[(long)blockIdx.x * c8 * 8 + (cbase + threadIdx.x) * 8 + e] = s_;      // row per (sample, chunk): folded by csbsr_sum_partials
+      }
+    }
+    __syncthreads();
+  }
+}
+extern "C" int csbsr_border_class_fill_masked_sums(const float* V, void* out, int64_t ld, const void* mask, int64_t mask_ld, float mask_slope, float* sums,
+                                                   int32_t N, int32_t H, int32_t W, int32_t c, csbsr_stream_t s) {
+  CSBSR_CHECK(V && out && mask && sums && c % 8 == 0, "border_class_fill_masked_sums: bad args");
+  if (!(H >= 3 && W >= 3 && (long)H * W >= 1024)) {      // tiny maps: the two stand-alone launches
+    if (int e = csbsr_border_class_fill_masked(V, out, ld, mask, mask_ld, mask_slope, N, H, W, c, s)) return e;
+    return csbsr_border_class_sums(mask, mask_ld, sums, N, H, W, c, s);
+  }
+  const long hw = (long)H * W;
+  int chunks = (int)((hw + 511) / 512);      // (the chunking of border_class_sums_impl)
+  if (chunks > 2048) chunks = 2048;
+  const long n_tot = (long)N * chunks * c, n_edge = (long)N * 4 * BCS_SEG * 3 * c;
+  float* part = csbsr_red_scratch(n_tot + n_edge);
+  CSBSR_NEED_SCRATCH(part, "border_class_fill_masked_sums");
+  hipLaunchKernelGGL(bcs_fill_total_kernel, dim3(N * chunks), dim3(256), 0, ST(s), V, (half_t*)out, (long)ld, (const half_t*)mask, (long)mask_ld, mask_slope,
+                     H, W, c / 8, chunks, part);
+  if (csbsr_sum_partials_batched(part, chunks, c, c, sums, N, 16l * c, ST(s))) return 1;
+  bcs_border_classes(mask, mask_ld, sums, N, H, W, c, part + n_tot, s);
+  CSBSR_LAUNCH_CHECK("csbsr_border_class_fill_masked_sums");
+  return 0;
 }
 extern "C" int csbsr_border_class_sums_prelu(const void* x, int64_t ld, const void* t, int64_t t_ld, float* sums, float* negdot, int32_t N, int32_t H,
                                              int32_t W, int32_t c, csbsr_stream_t s) {

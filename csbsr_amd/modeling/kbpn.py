@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from ..engine import FM, Conv, ShuffleConv, grad_acc, pad8, _ptr
 from .blocks import act_bwd, sft_bwd
+from .kp_bwd import const_wgrad_ok, fold_const_wgrad, pair1x1_backward, pair1x1_ok
 from .shapes import CONV_SETTING
 
 A_NONE, A_RELU, A_LRELU, A_PRELU, A_SIG = L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU, L.ACT_PRELU, L.ACT_SIGMOID
@@ -162,6 +163,10 @@ class KBPN:
         self.training_mode = True      # set by the owner (nn.Module.training of the model)
         self._gather = {}
         self.gather = os.environ.get("CSBSR_GATHER_DCH", "1") != "0"      # backward: gather each stage's slice of d(concat_h) (see _gather_conv)
+        # backward of the per-stage kernel predictor: fe_cat.2's weight gradient from the class sums its dgrad fold streams anyway, fe_cat.0's
+        # and fe_SR.1's from the pass that computes their input gradient (kp_bwd.py).  Bit 0: the fe_cat.2 fold, bit 1: the 1x1 pairs (the
+        # hook takes 0-3 for same-run A/B of either part); 0: a stand-alone weight-gradient launch each
+        self.kp_pairs = int(os.environ.get("CSBSR_KP_BWD_PAIRS", "3"))
         self.Mtap = border_tap_mask().to(eng.device)       # folded constant-operand convs: see _kernel_branch_fwd / Conv.fwd_folded
         self.Rtap = ring_tap_classes().to(eng.device)
 
@@ -597,25 +602,39 @@ class KBPN:
                 a.append(c.fwd(a[-1]))
         B = dk2.shape[0]
         d49 = torch.einsum("bk,bkc->bc", dk2, q["kp_map"]) / float(H * W)
-        g = self._bcast_grad(d49, H, W)
         cat2, cat1, cat0 = st.fe_cat[2], st.fe_cat[1], st.fe_cat[0]
         # Every layer of this branch is a bias-free conv + ReLU / LeakyReLU with a single consumer, so each dgrad applies the activation
         # derivative of the layer below in its own epilogue (mask = that layer's saved output): what a dgrad writes IS the next
         # dPre, and the ten stand-alone HR epilogue-backward passes per stage (read dOut, read out, write dPre) are gone.
         msk = lambda conv, out: (out, 0.0 if conv.act == A_RELU else conv.slope)
-        self._wg(cat2, g, c2)
-        dc2 = self._fold_const_dgrad(cat2, d49, msk(cat1, c2), H, W)
+        fold, pairs = int(self.kp_pairs) & 1, int(self.kp_pairs) & 2
+        if fold and not cat2.frozen and const_wgrad_ok(cat2):
+            # dPre of fe_cat.2 is constant per sample: its weight gradient folds onto the 16 border-class sums of c2, which the dgrad's
+            # masked fill reads as its mask -- one pass, no convolution against a constant
+            sums = e.f32(B, 16, c2.cp)
+            dc2 = self._fold_const_dgrad(cat2, d49, msk(cat1, c2), H, W, sums=sums)
+            fold_const_wgrad(cat2, d49, sums, self.Mtap)
+        else:
+            self._wg(cat2, self._bcast_grad(d49, H, W), c2)
+            dc2 = self._fold_const_dgrad(cat2, d49, msk(cat1, c2), H, W)
         self._wg(cat1, dc2, c1)
         dc1 = cat1.bwd_input(dc2, mask=msk(cat0, c1))
         del dc2
-        if not cat0.frozen:
-            cat0.bwd_weights(dc1, a[-1], split_override=(cat0.split[0], 0))
-        da = cat0.bwd_input(dc1, seg=0, mask=msk(st.fe_sr[4], a[5]))
+        mslope = msk(st.fe_sr[4], a[5])[1]
+        if pairs and not cat0.frozen and pair1x1_ok(cat0, dc1, a[5]):
+            da = pair1x1_backward(cat0, dc1, a[5], mslope)      # dgrad and the unfolded half's weight gradient from one read of (dc1, a5)
+        else:
+            if not cat0.frozen:
+                cat0.bwd_weights(dc1, a[-1], split_override=(cat0.split[0], 0))
+            da = cat0.bwd_input(dc1, seg=0, mask=msk(st.fe_sr[4], a[5]))
         dkin = self._kernel_branch_bwd(st, dc1, kctx, H, W)      # the fe_kernel branch: 25 class sums of dPre + a tiny autograd graph
         del dc1
         # fe_SR chain
         for i in (4, 3, 2, 1, 0):
             c = st.fe_sr[i]
+            if i > 0 and pairs and not c.frozen and pair1x1_ok(c, da, a[i]):
+                da = pair1x1_backward(c, da, a[i], msk(st.fe_sr[i - 1], a[i])[1])
+                continue
             self._wg(c, da, a[i])
             if i > 0:
                 da = c.bwd_input(da, mask=msk(st.fe_sr[i - 1], a[i]))
@@ -664,11 +683,12 @@ class KBPN:
                     grad_acc(conv.w).add_(g)
         return grads[0]
 
-    def _fold_const_dgrad(self, conv, gvec, mask, H, W):
+    def _fold_const_dgrad(self, conv, gvec, mask, H, W, sums=None):
         """dgrad of a zero-padded 3x3 conv whose dOut is spatially constant per sample (``gvec`` [B, cout]: the backward of the global
         average pool behind fe_cat.2, kbpn.py:573-578): dIn takes one value per border class -- T = g . W per tap, the 16 class
         sums with the taps flipped -- times the activation derivative of the layer below (``mask`` = (its saved output, slope)).
-        Replaces a 2*H*W*cin*cout*9 FLOP convolution of a constant map by a masked fill."""
+        Replaces a 2*H*W*cin*cout*9 FLOP convolution of a constant map by a masked fill.  ``sums`` (zeroed fp32 [B, 16, cp]): also
+        receives the 16 border-class sums of the mask map, taken in the same pass (the layer's input: kp_bwd.fold_const_wgrad)."""
         e = self.eng
         B = gvec.shape[0]
         w16 = conv.w.to(torch.float16).float()                      # same operand rounding as the MFMA path
@@ -682,5 +702,9 @@ class KBPN:
         out = e.new(B, H, W, conv.cin)
         mfm, mslope = mask
         assert mfm.cp == cp and (mfm.H, mfm.W) == (H, W) and not mfm.bcast
-        L.call("csbsr_border_class_fill_masked", _ptr(Vp), _ptr(out.t), out.ld, _ptr(mfm.t), mfm.ld, float(mslope), B, H, W, cp, e.stream)
+        if sums is not None:
+            L.call("csbsr_border_class_fill_masked_sums", _ptr(Vp), _ptr(out.t), out.ld, _ptr(mfm.t), mfm.ld, float(mslope), _ptr(sums), B, H, W, cp,
+                   e.stream)
+        else:
+            L.call("csbsr_border_class_fill_masked", _ptr(Vp), _ptr(out.t), out.ld, _ptr(mfm.t), mfm.ld, float(mslope), B, H, W, cp, e.stream)
         return out

@@ -84,7 +84,8 @@ def canon(name):
     m = re.search(r"conv_x3_kernelILi(\d)ELi(\d+)E", name) or re.search(r"conv_x3_kernel<(\d), (\d+)>", name)
     if m:
         return "conv_x3_kernel<%s>" % m.group(1) if m.group(2) == "0" else "conv_x3_kernel<%s,%s>" % m.groups()
-    for k in ("conv_wgrad_hr_kernel", "conv_wgrad_thin_kernel", "conv_wgrad_kernel", "conv_thin_cout_kernel", "conv_thin_cin2_kernel", "conv_thin_cin_kernel",
+    # (conv_pair1x1_kernel, bcs_fill_total_kernel: the per-stage kernel predictor's backward, csbsr_amd/modeling/kp_bwd.py)
+    for k in ("conv_pair1x1_kernel", "bcs_fill_total_kernel", "conv_wgrad_hr_kernel", "conv_wgrad_thin_kernel", "conv_wgrad_kernel", "conv_thin_cout_kernel", "conv_thin_cin2_kernel", "conv_thin_cin_kernel",
               "conv_thin_tpd_kernel", "conv_thin_tp_kernel", "conv_thin_sc_kernel", "thin_tp_bwd_kernel", "epilogue_bwd_kernel", "unpack_wgrad_kernel",
               "head1_fwd_kernel", "head1_bwd_input_kernel", "bn_bwd_apply_kernel", "bn_bwd_reduce_kernel", "bn_apply_kernel", "channel_mean_sub_kernel", "round_weights_kernel"):
         if k in name:

@@ -418,6 +418,11 @@ int csbsr_border_class_fill_masked(const float* V, void* out, int64_t ld, const 
                                    int32_t H, int32_t W, int32_t c, csbsr_stream_t s);
 int csbsr_border_class_sums(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c,
                             csbsr_stream_t s);
+/* csbsr_border_class_fill_masked, and in the same pass over the mask map its 16 border-class sums: sums[n][class][:] += sum over the
+ * pixels of that class of mask[n,y,x,:] (fp32 [N][16][c], zeroed by the caller) -- bit-identical to csbsr_border_class_sums(mask, ..).
+ * The layer whose dgrad the fill is reads `mask` as its input, so these are the sums its weight gradient needs when dPre is constant. */
+int csbsr_border_class_fill_masked_sums(const float* V, void* out, int64_t ld, const void* mask, int64_t mask_ld, float mask_slope,
+                                        float* sums, int32_t N, int32_t H, int32_t W, int32_t c, csbsr_stream_t s);
 /* the same plus negdot[n][ch] += sum over the pixels with t <= 0 of x * t (t: a second fp16 map of the same geometry): with x = dPre and
  * t = the saved output of a PReLU layer, sum(negdot) / slope^2 is that layer's slope gradient (blocks.py:105-120, the SFTLikeBlock's
  * conv_scale.0 / conv_shift.0 whose activation derivative rode on the dgrad above as csbsr_conv_desc_t::mask + mask_prelu).  Maps of >= 1024 pixels. */
@@ -646,6 +651,17 @@ int csbsr_thin_tp_backward(const void* dout, int64_t d_sn, int64_t d_sy, int64_t
                            int64_t x_sx, const void* wt_packed, int32_t cin, int32_t cout, int32_t stride, int32_t pad,
                            const float* prelu, int32_t N, int32_t h, int32_t w, void* dpre, int64_t p_sn, int64_t p_sy, int64_t p_sx,
                            float* slabs, float* dprelu_part, csbsr_stream_t s);
+/* Input gradient and weight gradient of a full-resolution 1x1 layer with 49 (stored as 56) input and 32 output channels, stride 1, no
+ * bias, in ONE pass over the two maps both need (the kernel predictor's fe_SR.1 and fe_cat.0, kbpn.py:521-578; csrc/conv_pair.hip):
+ *   din [N, H, W, 56] fp16 = (dpre . W) * (x > 0 ? 1 : mask_slope) -- bit-identical to csbsr_conv_hr_forward on the dgrad descriptor with
+ *   mask = x; wt_packed is that launch's operand (csbsr_pack_weights_hr, kind 1, c_real = 32, rows_real = the real input channels);
+ *   slabs: csbsr_conv_pair1x1_slabs(N, H, W, s) fp32 slabs [32][56] of sum_pix dpre[pix][o] * x[pix][c] in csbsr_conv_wgrad's layout
+ *   (fold with csbsr_unpack_wgrad(.., A = 32, KH = KW = 1, seg0 = the real input channels, .., splits = that count, ca_padded = 32)).
+ * dpre [N, H, W, 32], x [N, H, W, 56]; strides in elements; the slab count depends on the stream's CU budget: ask with the same stream. */
+int32_t csbsr_conv_pair1x1_slabs(int32_t N, int32_t H, int32_t W, csbsr_stream_t s);
+int csbsr_conv_pair1x1_backward(const void* dpre, int64_t a_sn, int64_t a_sy, int64_t a_sx, const void* x, int64_t b_sn, int64_t b_sy,
+                                int64_t b_sx, const void* wt_packed, float mask_slope, int32_t N, int32_t H, int32_t W, void* din,
+                                int64_t o_sn, int64_t o_sy, int64_t o_sx, float* slabs, csbsr_stream_t s);
 /* 1 if csbsr_conv_forward takes this descriptor with split_fused = 1 (the fused three-product stage of a split-fp16 input exists only in the
  * LDS-DMA kernels); 0: pack the three-block operand (csbsr_pack_weights_split layout 0) and clear split_fused */
 int32_t csbsr_conv_split_fused_eligible(const csbsr_conv_desc_t* d);
