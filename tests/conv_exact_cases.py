@@ -164,6 +164,8 @@ REQUIRED_VARIANTS = {
 # entry points: Conv's public fwd* / bwd* methods (read from csbsr_amd/engine.py by the coverage test), the subclasses of Conv, and the
 # operand modes that take separate kernel paths
 ROW_ENTRY = {"fwd": "Conv.fwd", "dgrad": "Conv.bwd_input", "wgrad": "Conv.bwd_weights", "classbias": "Conv.fwd_classbias"}
+# (the rows of tests/fused_exact_cases.py -- the paths with second outputs, the folded segment, ShuffleConv, kp_bwd -- name their entry
+# point themselves: FRow.entry; tests/test_conv_exact_coverage_cpu.py counts both tables)
 REQUIRED_MODES = ("sigmoid", "split")
 
 _SPLIT = ("split-precision (hi + lo) operands need a lattice reference of their own -- x_lo planes, the round-to-nearest weight split, "
@@ -171,12 +173,6 @@ _SPLIT = ("split-precision (hi + lo) operands need a lattice reference of their 
 NOT_COVERED = {
     "GLDS64/1": _SPLIT, "GLDS64/3": _SPLIT, "GLDS128/1": _SPLIT, "GLDS128/3": _SPLIT,
     "GLDS256/1": _SPLIT, "GLDS256/3": _SPLIT, "GLDS256W/1": _SPLIT, "GLDS256W/3": _SPLIT,
-    "split": _SPLIT + " (fwd_blocks 1 / 2 / 3, split output slices, Conv._wq / Conv._dc_bias on exact weights)",
-    "TP/14": "the fused bias / PReLU-slope sums of the layer below (dact): its reference and frozen-layer handling are not in the table yet: a follow-up",
-    "TP/13": "the same sums with the residual layer's d(res) output (dres): a follow-up",
-    "Conv.fwd_folded": "the constant kernel-code segment as a 16-class bias built from fp32 mat-vecs of the master weights: a follow-up",
-    "Conv.bwd_weights_folded": "the border-class sums of the folded segment are torch einsums around a Conv.bwd_weights launch: a follow-up",
-    "Conv.fwd_const_1x1": "the constant segment as a per-sample bias row (used with split inputs): a follow-up together with the split rows",
-    "Conv.bwd_thin_tp_fused": "csrc/conv_kbup.hip rebuilds the pre-activation and sums PReLU-slope partials: its own reference, a follow-up",
-    "ShuffleConv": "a weight permutation around the transposed-conv kernels the table covers: a follow-up",
+    "split": _SPLIT + " (fwd_blocks 1 / 2 / 3, split output slices, Conv._wq / Conv._dc_bias on exact weights, and the split-input forms of "
+                      "Conv.fwd_folded and Conv.fwd_const_1x1, whose plain-input forms have rows in tests/fused_exact_cases.py)",
 }

@@ -2,8 +2,9 @@
 the weight-gradient kernel IDs (``enum WGRADK_*``, csrc/conv_wgrad.h) are parsed from the sources and each must be the ``kid`` of a row
 of tests/conv_exact_cases.py -- or be listed in its EXCLUDED with a reason.  A new kernel therefore arrives with an exact test.  The same
 holds for the template instances the dispatchers build (REQUIRED_VARIANTS), the engine's entry points into the kernels (Conv's fwd* /
-bwd* methods and subclasses, read from csbsr_amd/engine.py) and the sigmoid / split operand modes: each has a row or a NOT_COVERED
-reason, so what the table leaves out is written down next to it.  The debug-mode defaults the GPU test restores are checked against
+bwd* methods and subclasses, read from csbsr_amd/engine.py; the public functions of csbsr_amd/modeling/kp_bwd.py other than its ``*_ok``
+predicates) and the sigmoid / split operand modes: each has a row -- here or in tests/fused_exact_cases.py, whose rows name their entry
+point -- or a NOT_COVERED reason, so what the tables leave out is written down next to them.  The debug-mode defaults the GPU test restores are checked against
 the sources' initial values."""
 import os
 import re
@@ -11,6 +12,7 @@ import re
 import pytest
 
 from conv_exact_cases import DEFAULT_MODES, EXCLUDED, NOT_COVERED, REQUIRED_MODES, REQUIRED_VARIANTS, ROW_ENTRY, ROWS
+from fused_exact_cases import FUSED_ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "csbsr_amd", "csrc")
@@ -72,18 +74,25 @@ def entry_points():
     body = re.search(r"^class Conv\b.*?(?=^class |\Z)", src, re.S | re.M).group(0)
     meths = ["Conv." + m for m in re.findall(r"^    def ((?:fwd|bwd)\w*)\(", body, re.M)]
     subs = re.findall(r"^class (\w+)\(Conv\)", src, re.M)
-    return meths + subs
+    with open(os.path.join(ROOT, "csbsr_amd", "modeling", "kp_bwd.py")) as f:
+        kp = ["kp_bwd." + m for m in re.findall(r"^def ([a-z]\w*)\(", f.read(), re.M) if not m.endswith("_ok")]
+    return meths + subs + kp
 
 
-def missing_paths(rows, not_covered):
+def _instances(rows, fused):
+    """(kernel ID, template instance) pairs the rows of both tables assert"""
+    return {(r.kid, r.var) for r in rows if r.op != "wgrad"} | {(r.kid, r.var) for r in fused if isinstance(r.kid, int)}
+
+
+def missing_paths(rows, not_covered, fused=FUSED_ROWS):
     """the template instances (REQUIRED_VARIANTS), entry points and operand modes with neither a row nor a NOT_COVERED reason"""
-    have = {(r.kid, r.var) for r in rows if r.op != "wgrad"}
+    have = _instances(rows, fused)
     miss = []
     for fam, (kid, vars_) in REQUIRED_VARIANTS.items():
         for v in vars_:
             if (kid, v) not in have and f"{fam}/{v}" not in not_covered:
                 miss.append(f"{fam}/{v}")
-    ops = {ROW_ENTRY[r.op] for r in rows}
+    ops = {ROW_ENTRY[r.op] for r in rows} | {r.entry for r in fused}
     for ep in entry_points():
         if ep not in ops and ep not in not_covered:
             miss.append(ep)
@@ -102,7 +111,7 @@ def test_every_instance_and_entry_point_has_a_row_or_a_reason():
 def test_not_covered_is_current():
     """every NOT_COVERED entry names a real path that really has no row (a row added later must take its entry out)"""
     eps = set(entry_points())
-    have = {(r.kid, r.var) for r in ROWS if r.op != "wgrad"}
+    have = _instances(ROWS, FUSED_ROWS)
     for name, why in NOT_COVERED.items():
         assert isinstance(why, str) and len(why.split()) >= 6, f"NOT_COVERED[{name}] needs a written reason"
         if "/" in name:
@@ -112,16 +121,34 @@ def test_not_covered_is_current():
         elif name in REQUIRED_MODES:
             assert name not in {m for r in ROWS for m in r.epi.split("_")}, f"NOT_COVERED[{name}] has a row"
         else:
-            assert name in eps and name not in {ROW_ENTRY[r.op] for r in ROWS}, f"NOT_COVERED[{name}]: no such entry point, or it has a row"
+            assert name in eps and name not in {ROW_ENTRY[r.op] for r in ROWS} | {r.entry for r in FUSED_ROWS}, \
+                f"NOT_COVERED[{name}]: no such entry point, or it has a row"
+
+
+def test_not_covered_is_down_to_the_split_precision_entries():
+    assert set(NOT_COVERED) == {f"{fam}/{v}" for fam in ("GLDS64", "GLDS128", "GLDS256", "GLDS256W") for v in (1, 3)} | {"split"}
+    assert "fwd_folded" in NOT_COVERED["split"] and "fwd_const_1x1" in NOT_COVERED["split"]
+
+
+def test_fused_rows_name_real_entry_points():
+    eps = set(entry_points())
+    for r in FUSED_ROWS:
+        assert r.entry in eps, f"{r.name}: {r.entry} is no entry point of csbsr_amd/engine.py or csbsr_amd/modeling/kp_bwd.py"
 
 
 def test_the_path_check_names_what_is_missing():
     """dropping a row, a reason, or a new Conv method shows up by name"""
     assert missing_paths([r for r in ROWS if r.name != "x3n_narrow_bn"], NOT_COVERED) == ["X3N/3"]
     nc = dict(NOT_COVERED)
-    del nc["ShuffleConv"]
-    assert missing_paths(ROWS, nc) == ["ShuffleConv"]
-    assert "Conv.fwd_classbias" in entry_points() and "Conv.bwd_thin_tp_fused" in entry_points()
+    del nc["split"]
+    assert missing_paths(ROWS, nc) == ["split"]
+    assert "Conv.fwd_classbias" in entry_points() and "Conv.bwd_weights_folded" in entry_points()
+    # ... and so does dropping the rows of the second table, or one of them, or a new public function of kp_bwd.py
+    assert missing_paths(ROWS, NOT_COVERED, fused=[]) == ["TP/14", "TP/13", "Conv.fwd_folded", "Conv.fwd_const_1x1", "Conv.bwd_weights_folded",
+                                                         "Conv.bwd_thin_tp_fused", "ShuffleConv", "kp_bwd.fold_const_wgrad", "kp_bwd.pair1x1_backward"]
+    assert missing_paths(ROWS, NOT_COVERED, fused=[r for r in FUSED_ROWS if r.group != "shuffle"]) == ["ShuffleConv"]
+    assert missing_paths(ROWS, NOT_COVERED, fused=[r for r in FUSED_ROWS if r.name != "tp_dact"]) == ["TP/14"]
+    assert "kp_bwd.pair1x1_ok" not in entry_points() and "kp_bwd.const_wgrad_ok" not in entry_points()
 
 
 def test_exclusions_carry_a_reason():
