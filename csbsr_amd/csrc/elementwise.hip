@@ -1741,7 +1741,8 @@ __global__ void border_class_fill_kernel(const float* V, half_t* out, long ld, i
     *reinterpret_cast<h8*>(out + (((long)n * H + y) * W + x) * ld + cc * 8) = o;
   }
 }
-// adjoint: sums[n][class][:] += sum over the pixels of that class of x[n,y,x,:].  Degenerate / tiny maps: ONE workgroup per sample,
+// adjoint: sums[n][class][:] += sum over the pixels of that class of x[n,y,x,:] (both paths ACCUMULATE: the caller zeroes sums before the
+// first call).  Degenerate / tiny maps: ONE workgroup per sample,
 // a thread owns a channel octet and walks the pixels in raster order (fixed order, no atomics).
 __global__ __launch_bounds__(256) void border_class_sums_small_kernel(const half_t* x, long ld, float* sums, int H, int W, int c8) {
   const int n = blockIdx.x;
@@ -1885,34 +1886,45 @@ __global__ __launch_bounds__(256) void bcs_edges_kernel(const half_t* x, long ld
       }
   }
 }
-// sums[n][cls][ch] += the edge / corner sums of the segments, in segment order (cls = border-class index of conv_epilogue_row)
-__global__ void bcs_edges_finish_kernel(const float* part, float* sums, int N, int c) {
+// border class of bin k (0 the edge proper, 1 its x == 0 corner, 2 its x == W - 1 corner) of edge 0 .. 3 (top, bottom, left, right): the one
+// map both kernels below use
+__device__ __forceinline__ int bcs_cls(int edge, int k) {
+  const int base_cls = edge == 0 ? 8 : (edge == 1 ? 4 : (edge == 2 ? 2 : 1));
+  return base_cls + (k == 1 ? 2 : (k == 2 ? 1 : 0));
+}
+// sums[n][cls][ch] += the edge / corner sums of the segments, in segment order (cls = border-class index of conv_epilogue_row).  The folded
+// sum also goes back into the row of segment 0 (read by this thread alone), where bcs_fixup_kernel finds THIS call's border sums.
+__global__ void bcs_edges_finish_kernel(float* part, float* sums, int N, int c) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * 4 * 3 * c) return;
   const int ch = i % c; int r = i / c;
   const int k = r % 3; r /= 3;
   const int edge = r % 4; const int n = r / 4;
   if (edge >= 2 && k > 0) return;
-  const int base_cls = edge == 0 ? 8 : (edge == 1 ? 4 : (edge == 2 ? 2 : 1));
-  const int cls = base_cls + (k == 1 ? 2 : (k == 2 ? 1 : 0));
   float t = 0.f;
   for (int seg = 0; seg < BCS_SEG; ++seg) t += part[((((long)n * 4 + edge) * BCS_SEG + seg) * 3 + k) * c + ch];
-  sums[((long)n * 16 + cls) * c + ch] += t;
+  sums[((long)n * 16 + bcs_cls(edge, k)) * c + ch] += t;
+  part[(((long)n * 4 + edge) * BCS_SEG * 3 + k) * c + ch] = t;
 }
-__global__ void bcs_fixup_kernel(float* sums, int N, int c) {
+// class 0 holds (what it held before +) the total: take this call's border sums off it, in ascending class order 1, 2, 4, 5, 6, 8, 9, 10
+// (the host takes this path only for H, W >= 3, where no pixel falls into another class) -- not the content of sums[1 .. 15], which
+// includes whatever the caller had accumulated there
+__global__ void bcs_fixup_kernel(const float* part, float* sums, int N, int c) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * c) return;
   const int n = i / c, ch = i % c;
-  float* s_ = sums + (long)n * 16 * c + ch;
   float border = 0.f;
-  for (int k = 1; k < 16; ++k) border += s_[(long)k * c];
-  s_[0] -= border;
+  for (int cls = 1; cls <= 10; ++cls)
+    for (int edge = 0; edge < 4; ++edge)
+      for (int k = 0; k < (edge < 2 ? 3 : 1); ++k)
+        if (bcs_cls(edge, k) == cls) border += part[(((long)n * 4 + edge) * BCS_SEG * 3 + k) * c + ch];
+  sums[(long)n * 16 * c + ch] -= border;
 }
 // stages (2) and (3) of the fast path below: the border pixels binned per class, then interior = total - border (the totals are in class 0)
 static void bcs_border_classes(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c, float* epart, csbsr_stream_t s) {
   hipLaunchKernelGGL(bcs_edges_kernel, dim3(N * 4 * ((c / 8 + 31) / 32) * BCS_SEG), dim3(256), 0, ST(s), (const half_t*)x, (long)ld, epart, H, W, c / 8);
-  hipLaunchKernelGGL(bcs_edges_finish_kernel, dim3((N * 12 * c + 255) / 256), dim3(256), 0, ST(s), (const float*)epart, sums, N, c);
-  hipLaunchKernelGGL(bcs_fixup_kernel, dim3((N * c + 255) / 256), dim3(256), 0, ST(s), sums, N, c);
+  hipLaunchKernelGGL(bcs_edges_finish_kernel, dim3((N * 12 * c + 255) / 256), dim3(256), 0, ST(s), epart, sums, N, c);
+  hipLaunchKernelGGL(bcs_fixup_kernel, dim3((N * c + 255) / 256), dim3(256), 0, ST(s), (const float*)epart, sums, N, c);
 }
 static int border_class_sums_impl(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c, const void* t, int64_t t_ld,
                                   float* negdot, csbsr_stream_t s) {

@@ -408,7 +408,9 @@ int csbsr_instnorm_bwd(const void* dy, int64_t dy_ld, const float* x, const floa
 
 /* Constant-operand folding (exact): a zero-padded 3x3 conv of a spatially constant map (fe_kernel.0 applied to the
  * expanded kernel code, kbpn.py:565-567) takes one value per border class ((y==0)*8 + (y==H-1)*4 + (x==0)*2 + (x==W-1)).
- * fill: out[n,y,x,:] = V[n][class][:] (fp32 [N][16][c] -> fp16 NHWC);  sums: its adjoint (sums zeroed by the caller). */
+ * fill: out[n,y,x,:] = V[n][class][:] (fp32 [N][16][c] -> fp16 NHWC);  sums: its adjoint.
+ * Every *_sums entry point below ACCUMULATES: sums[n][class][:] += this call's class sums (negdot likewise), whatever the map size; a
+ * caller that wants the plain sums zeroes the buffer first, one that adds up several maps calls again on the same buffer. */
 int csbsr_border_class_fill(const float* V, void* out, int64_t ld, int32_t N, int32_t H, int32_t W, int32_t c,
                             csbsr_stream_t s);
 /* The same fill for the adjoint direction: the dgrad of a 3x3 conv whose dOut is spatially constant (the backward of a global average
@@ -419,7 +421,7 @@ int csbsr_border_class_fill_masked(const float* V, void* out, int64_t ld, const 
 int csbsr_border_class_sums(const void* x, int64_t ld, float* sums, int32_t N, int32_t H, int32_t W, int32_t c,
                             csbsr_stream_t s);
 /* csbsr_border_class_fill_masked, and in the same pass over the mask map its 16 border-class sums: sums[n][class][:] += sum over the
- * pixels of that class of mask[n,y,x,:] (fp32 [N][16][c], zeroed by the caller) -- bit-identical to csbsr_border_class_sums(mask, ..).
+ * pixels of that class of mask[n,y,x,:] (fp32 [N][16][c], accumulated as above) -- bit-identical to csbsr_border_class_sums(mask, ..).
  * The layer whose dgrad the fill is reads `mask` as its input, so these are the sums its weight gradient needs when dPre is constant. */
 int csbsr_border_class_fill_masked_sums(const float* V, void* out, int64_t ld, const void* mask, int64_t mask_ld, float mask_slope,
                                         float* sums, int32_t N, int32_t H, int32_t W, int32_t c, csbsr_stream_t s);
