@@ -174,6 +174,11 @@ SIGNATURES = {
     "csbsr_surface_prepare": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "csbsr_surface_gather": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp]),
     "csbsr_pr_sweep": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "csbsr_skeleton_max_passes": (i32, []),
+    "csbsr_skeleton_init": (i32, [vp, f32, i32, i32, i32, vp, vp]),
+    "csbsr_skeleton_passes": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "csbsr_skeleton_finish": (i32, [vp, i32, i32, i32, vp, vp]),
+    "csbsr_centerline_counts": (i32, [vp, vp, f32, vp, vp, i32, i32, i32, vp, vp]),
     "csbsr_head1_fwd": (i32, [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp]),
     "csbsr_head1_bwd_input": (i32, [vp, i64, vp, i32, vp, i64, i64, vp]),
     "csbsr_adam_step": (i32, [vp, vp, vp, i32, C.c_double, C.c_double, C.c_float, vp]),

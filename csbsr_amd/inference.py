@@ -3,10 +3,11 @@
 image, PSNR of the kernel, and the IoU of the segmentation map at every threshold 0.01 .. 0.99 -- without the [B,99,H,W] broadcast
 tensor and the host numpy reductions.  ``evaluate_dataset`` runs it over a whole HBM-resident test set (csbsr_amd/data/resident_test.py) and
 returns the reference's final report, with the saved images and masks leaving the device as uint8 (csrc/eval_io.hip); on request
-(``pr_tolerance``) also the tolerance-matched precision / recall / F of the map over the same thresholds (csrc/pr_sweep.hip), which the
-reference does not compute.
+(``pr_tolerance``) also the tolerance-matched precision / recall / F of the map over the same thresholds (csrc/pr_sweep.hip), and
+(``cldice_threshold``) the centerline Dice of the map at one threshold (csrc/skeleton.hip), neither of which the reference computes.
 ``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
-of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device."""
+of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device; on request (``measure_threshold``) with the
+crack's area, centerline length and mean width per image."""
 import csv
 import os
 
@@ -17,6 +18,7 @@ from . import _lib as L
 from .data.patch_sampler import JointPatch
 from .engine import _ptr
 from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep, pr_sweep, pr_tol2
+from .utils.estimate_metrics import skeletonize, centerline_counts, cldice_scores, summarize_cldice, unit_threshold
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -32,14 +34,18 @@ def _kernel_for_psnr(model, kernel_preds, kernel_targets):
 
 @torch.no_grad()
 def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, masks, kernel_targets, ksize, thresholds=THRESHOLDS,
-                   surface_distance=False, pr_tolerance=None):
+                   surface_distance=False, pr_tolerance=None, cldice_threshold=None):
     """imgs [B, nPatch, 3, h, w] LR patches (as CrackDataSetTest delivers them), kernel_targets [B, nPatch, K, K];
     returns dict(sr_preds, segment_preds, psnr [B], ssim [B], kernel_psnr [B*nPatch], iou [B, T]) -- numpy arrays for the metrics.
     surface_distance=True adds hd [B, T], msd [B, T] (float64) and the counters hd_outliers, msd_outliers of calc_distance_metrics
     (inference.py:293-336) at the same thresholds.  pr_tolerance = a radius in pixels adds pr_counts [B, 4, T] (int64), the tolerance-matched
-    precision / recall counts of ``pr_sweep`` (scores: ``pr_scores``, ``summarize_pr``); None adds nothing."""
+    precision / recall counts of ``pr_sweep`` (scores: ``pr_scores``, ``summarize_pr``); None adds nothing.  cldice_threshold = a float
+    strictly inside (0, 1) adds cl_counts [B, 4] (int64), the centerline counts of ``centerline_counts`` at that one threshold (scores:
+    ``cldice_scores``, ``summarize_cldice``); None adds nothing."""
     if pr_tolerance is not None:
         pr_tol2(pr_tolerance)
+    if cldice_threshold is not None:
+        cldice_threshold = unit_threshold(cldice_threshold, "cldice_threshold")
     joint = JointPatch()
     imgs = imgs.view(-1, *imgs.shape[2:])
     kernel_targets = kernel_targets.view(-1, 1, *kernel_targets.shape[2:])
@@ -58,6 +64,8 @@ def evaluate_batch(model, imgs, img_unfold_shape, seg_unfold_shape, sr_targets, 
         out.update(surface_distance_sweep(segment_preds, masks, thresholds))
     if pr_tolerance is not None:
         out["pr_counts"] = pr_sweep(segment_preds, masks, thresholds, pr_tolerance).cpu().numpy().astype(np.int64)
+    if cldice_threshold is not None:
+        out["cl_counts"] = centerline_counts(segment_preds, masks, cldice_threshold).cpu().numpy().astype(np.int64)
     return out
 
 
@@ -213,6 +221,34 @@ def write_pr_log(path, counts, thresholds, fnames):
                 w.writerow([name, tag] + [repr(float(v)) for v in a[i]])
 
 
+# ------------------------------------------------------------------------------------------------ centerlines
+def write_cldice_log(path, counts, fnames):
+    """cldice_log.csv: one row per image -- the four counts of ``centerline_counts`` and the three scores of ``cldice_scores`` (repr: the
+    shortest text that reads back to the same fp64)."""
+    c = np.asarray(counts, dtype=np.int64)
+    assert c.shape == (len(fnames), 4)
+    tp, ts, cl = cldice_scores(c)
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["", "skel_pred", "skel_pred_in_gt", "skel_gt", "skel_gt_in_pred", "Tprec", "Tsens", "clDice"])
+        for i, name in enumerate(fnames):
+            w.writerow([name] + [int(v) for v in c[i]] + [repr(float(a[i])) for a in (tp, ts, cl)])
+
+
+def mean_width(crack_px, skeleton_px):
+    """crack_px / skeleton_px in fp64, 0.0 for an empty skeleton"""
+    return float(crack_px) / float(skeleton_px) if skeleton_px else 0.0
+
+
+def write_crack_stats(path, rows):
+    """crack_stats.csv: (name, crack_px, skeleton_px, mean_width_px) per image"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["name", "crack_px", "skeleton_px", "mean_width_px"])
+        for name, crack, skel, width in rows:
+            w.writerow([name, int(crack), int(skel), repr(float(width))])
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -220,12 +256,13 @@ class _Saver:
 
     A batch is (img [B,H,W,3], raw [B,H,W,1], planes [B,S,H,W], kern [B * nP,1,K,K]) of equal images, or, with ``layout`` = one
     (pixel offset, H, W, first kernel, kernels) per image, flat pools of images of any size: img [3 * npix] interleaved per image, raw [npix],
-    planes [1,S,npix], kern [sum of kernels,1,K,K]."""
+    planes [1,S,npix], kern [sum of kernels,1,K,K].  With ``skeletons`` a fifth tensor follows, skel [npix] of 0 / 255 laid out like raw, and
+    goes to skeletons/<name>."""
 
-    def __init__(self, save_dir, thresholds):
+    def __init__(self, save_dir, thresholds, skeletons=False):
         self.dir = save_dir
         self.th_names = [f"th_{thresholds[i]:.2f}" for i in SAVE_THRESHOLD_IDX if i < len(thresholds)] + ["th_-1.00"]
-        for d in ["images", "kernels", "kernels_origin"] + [os.path.join("masks", t) for t in self.th_names]:
+        for d in ["images", "kernels", "kernels_origin"] + [os.path.join("masks", t) for t in self.th_names] + ["skeletons"] * bool(skeletons):
             os.makedirs(os.path.join(save_dir, d), exist_ok=True)
         self.ring, self.n, self.pending = [None] * _SLOTS, 0, []
 
@@ -250,9 +287,11 @@ class _Saver:
     def drain(self, keep=0):
         from PIL import Image
         while len(self.pending) > keep:
-            fnames, (img, raw, planes, kern), ev, layout = self.pending.pop(0)
+            fnames, views, ev, layout = self.pending.pop(0)
+            img, raw, planes, kern = views[:4]
             ev.synchronize()                                 # this slot's copies only
             img, raw, planes = img.numpy(), raw.numpy(), planes.numpy()
+            skel = views[4].numpy() if len(views) > 4 else None
             nP = kern.shape[0] // len(fnames)
             for b, name in enumerate(fnames):
                 if layout is None:
@@ -265,6 +304,9 @@ class _Saver:
                 for j, t in enumerate(self.th_names[:-1]):
                     Image.fromarray(planes_b[j]).save(os.path.join(self.dir, "masks", t, name))
                 Image.fromarray(raw_b).save(os.path.join(self.dir, "masks", "th_-1.00", name))
+                if skel is not None:
+                    o, H, W = layout[b][:3]
+                    Image.fromarray(skel[o:o + H * W].reshape(H, W)).save(os.path.join(self.dir, "skeletons", name))
                 stem = name.replace(".png", "")
                 for j in range(nP):                          # save_kernel: 441 values per patch, on the host
                     k = kern[k0 + j]
@@ -275,7 +317,7 @@ class _Saver:
 
 @torch.no_grad()
 def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_distance=False, classification=False, save_dir=None,
-                     pr_tolerance=None):
+                     pr_tolerance=None, cldice_threshold=None):
     """``inference_for_ss`` (model/engine/inference.py:25-207) over a ``DeviceTestLoader``: per batch the computation of ``evaluate_batch``
     -- with the stitch, the clip and the 8-bit quantisation in one kernel (csbsr_stitch_clip_u8) instead of JointPatch's copy and two masked
     assignments -- accumulated into the reference's final report.  ``model`` is any callable with JointModel's evaluation signature.
@@ -286,11 +328,16 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
     host).  ``summary`` is ``summarize`` of those arrays.  ``pr_tolerance`` = a radius in pixels adds pr_counts [N, 4, T] int64 -- per image
     and threshold (n_pred, tp_pred, tp_gt, n_gt) of ``pr_sweep``: a predicted pixel counts when a ground-truth pixel lies within the
     radius, and the other way round -- and the keys of ``summarize_pr`` (ODS, ODS_threshold, OIS, AP, P_at_ODS, R_at_ODS) to ``summary``;
-    None (the default) adds nothing.
+    None (the default) adds nothing.  ``cldice_threshold`` = a float strictly inside (0, 1) adds cl_counts [N, 4] int64 -- per image
+    (|S_P|, |S_P & V_L|, |S_L|, |S_L & V_P|) of ``centerline_counts``, S the Guo-Hall skeletons of the map binarised at that threshold and of
+    the mask -- and the keys of ``summarize_cldice`` (clDice, Tprec, Tsens, clDice_pooled) to ``summary``; None (the default) adds nothing.
+    It is ONE threshold, not the sweep: the binary maps of the 99 thresholds are nested, their skeletons are not, so a sweep would be 99
+    thinnings per image.
 
     ``save_dir`` writes what ``test.py --sf_save_image`` writes: images/<fname>, masks/th_<t:.2f>/<fname> for the threshold indices
     [0, 9, 19, ..., 89, 98], masks/th_-1.00/<fname> for the raw map, kernels/<stem>_<j>.png, kernels_origin/<stem>_<j>_origin.png, and
-    iou_log.csv (and, with ``pr_tolerance``, pr_log.csv next to it: ``write_pr_log``).  Images and masks leave the device as uint8
+    iou_log.csv (and, with ``pr_tolerance``, pr_log.csv next to it: ``write_pr_log``; with ``cldice_threshold``, cldice_log.csv:
+    ``write_cldice_log``).  Images and masks leave the device as uint8
     (csbsr_stitch_clip_u8, csbsr_threshold_planes_u8) through pinned slots with non-blocking copies; PIL encodes batch k while the device runs batch k + 1, and the host waits on a slot's event only.  Without
     ``save_dir`` the metrics stay on the device until the last batch has been enqueued (the surface distances, whose second half is host
     work, excepted)."""
@@ -299,9 +346,11 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
         raise ValueError(f"classification metrics are taken at threshold index {CLASSIFICATION_IDX}: {len(thresholds)} thresholds given")
     if pr_tolerance is not None:
         pr_tol2(pr_tolerance)                                # a bad radius is refused before anything runs
+    if cldice_threshold is not None:
+        cldice_threshold = unit_threshold(cldice_threshold, "cldice_threshold")
     saver = _Saver(save_dir, thresholds) if save_dir is not None else None
     save_th = None
-    fnames, acc = [], {k: [] for k in ("psnr", "ssim", "kernel_psnr", "iou", "counts", "hd", "msd", "pr")}
+    fnames, acc = [], {k: [] for k in ("psnr", "ssim", "kernel_psnr", "iou", "counts", "hd", "msd", "pr", "cl")}
     hd_out = msd_out = 0
     for imgs, sr_targets, masks, kernel_targets, names, img_shape, seg_shape in loader:
         fnames += list(names)
@@ -322,6 +371,8 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
             acc["counts"].append(classification_counts(segment_preds, masks, th32[CLASSIFICATION_IDX].to(segment_preds.device)))
         if pr_tolerance is not None:
             acc["pr"].append(pr_sweep(segment_preds, masks, thresholds, pr_tolerance))
+        if cldice_threshold is not None:
+            acc["cl"].append(centerline_counts(segment_preds, masks, cldice_threshold))
         if saver is not None:
             if save_th is None:
                 save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(segment_preds.device)
@@ -349,16 +400,21 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
     if pr_tolerance is not None:
         out["pr_counts"] = torch.cat(acc["pr"]).cpu().numpy().astype(np.int64)
         out["summary"].update(summarize_pr(out["pr_counts"], thresholds))
+    if cldice_threshold is not None:
+        out["cl_counts"] = torch.cat(acc["cl"]).cpu().numpy().astype(np.int64)
+        out["summary"].update(summarize_cldice(out["cl_counts"]))
     if save_dir is not None:
         write_iou_log(os.path.join(save_dir, "iou_log.csv"), out["iou"], thresholds, fnames)
         if pr_tolerance is not None:
             write_pr_log(os.path.join(save_dir, "pr_log.csv"), out["pr_counts"], thresholds, fnames)
+        if cldice_threshold is not None:
+            write_cldice_log(os.path.join(save_dir, "cldice_log.csv"), out["cl_counts"], fnames)
     return out
 
 
 # ------------------------------------------------------------------------------------------------ prediction without ground truth
 @torch.no_grad()
-def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None):
+def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -371,8 +427,18 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     ``save_dir`` writes what ``evaluate_dataset`` writes, minus iou_log.csv -- images/<name>, masks/th_<t:.2f>/<name> for the threshold
     indices [0, 9, 19, ..., 89, 98] (one csbsr_threshold_planes_u8 launch over the unit's flat map pool), masks/th_-1.00/<name>,
     kernels/<stem>_<j>.png and kernels_origin/<stem>_<j>_origin.png, j over the image's tiles -- through the same ring of pinned slots; the
-    files of the last units are complete when the generator is exhausted."""
-    saver = _Saver(save_dir, thresholds) if save_dir is not None else None
+    files of the last units are complete when the generator is exhausted.
+
+    ``measure_threshold`` = a float strictly inside (0, 1) adds three keys to every yielded dict: crack_px (int), the pixels with
+    map_f32 - t > 0; skeleton_px (int), the size of that region's Guo-Hall skeleton (``skeletonize``) -- the crack's length in pixels --;
+    mean_width_px = crack_px / skeleton_px in fp64 (0.0 for an empty skeleton).  The skeleton is taken on the stitched map of the whole
+    image, never per tile, and the two integers of all the images of a work unit come back in one read.  With ``save_dir`` it also writes
+    skeletons/<name> (0 / 255) through the ring and, when the generator is exhausted, crack_stats.csv.  None (the default) adds nothing."""
+    measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
+    saver = None
+    if save_dir is not None:
+        saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
+    stats = []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -395,12 +461,30 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         kernels = torch.cat(kernels)
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
+        extra, px = [], None
+        if measure is not None:
+            skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
+            t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
+            px = []
+            for o, H, W, _, _ in layout:                     # one plane per image: the stitched map, never a tile
+                sk = skeletonize(map_f32[o:o + H * W].view(1, H, W), measure).view(-1)
+                skel_u8[o:o + H * W] = sk * 255
+                px.append(torch.stack([(map_f32[o:o + H * W] - t32 > 0).sum(), sk.sum()]))
+            px = torch.stack(px).cpu().tolist()              # the unit's integers in one read
+            extra = [skel_u8]
         if saver is not None:
             planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
-            saver.push(loader.names[unit.i0:unit.i1], [sr_u8, map_u8, planes, kernels], layout=layout)
+            saver.push(loader.names[unit.i0:unit.i1], [sr_u8, map_u8, planes, kernels] + extra, layout=layout)
             saver.drain(keep=1)                              # encode the unit before this one while the device runs this one
-        for i, (o, H, W, k0, nk) in zip(range(unit.i0, unit.i1), layout):
-            yield {"name": loader.names[i], "sr_u8": sr_u8[3 * o:3 * (o + H * W)].view(H, W, 3), "map_u8": map_u8[o:o + H * W].view(H, W),
-                   "map_f32": map_f32[o:o + H * W].view(H, W), "kernels": kernels[k0:k0 + nk]}
+        for j, (i, (o, H, W, k0, nk)) in enumerate(zip(range(unit.i0, unit.i1), layout)):
+            item = {"name": loader.names[i], "sr_u8": sr_u8[3 * o:3 * (o + H * W)].view(H, W, 3), "map_u8": map_u8[o:o + H * W].view(H, W),
+                    "map_f32": map_f32[o:o + H * W].view(H, W), "kernels": kernels[k0:k0 + nk]}
+            if px is not None:
+                crack, skel = int(px[j][0]), int(px[j][1])
+                item.update(crack_px=crack, skeleton_px=skel, mean_width_px=mean_width(crack, skel))
+                stats.append((loader.names[i], crack, skel, item["mean_width_px"]))
+            yield item
     if saver is not None:
         saver.drain()
+        if measure is not None:
+            write_crack_stats(os.path.join(save_dir, "crack_stats.csv"), stats)

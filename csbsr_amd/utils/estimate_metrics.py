@@ -101,6 +101,108 @@ def pr_sweep(segment_preds, masks, thresholds, tolerance=2.0):
     return out
 
 
+# ------------------------------------------------------------------------------------------- centerlines (skeleton, clDice)
+def skeleton_threshold(threshold, what="threshold"):
+    """the binarisation threshold of a skeleton as a Python float: a finite float (Python or NumPy), anything else is a ValueError"""
+    if not isinstance(threshold, (float, np.floating)) or not np.isfinite(threshold):
+        raise ValueError(f"{what} must be a finite float, got {threshold!r}")
+    return float(threshold)
+
+
+def unit_threshold(threshold, what):
+    """a threshold on a probability map: a float strictly inside (0, 1), anything else is a ValueError"""
+    t = skeleton_threshold(threshold, what)
+    if not 0.0 < t < 1.0:
+        raise ValueError(f"{what} must lie strictly inside (0, 1), got {threshold!r}")
+    return t
+
+
+def _skeleton_passes(max_passes):
+    if isinstance(max_passes, bool) or not isinstance(max_passes, (int, np.integer)) or max_passes < 0:
+        raise ValueError(f"max_passes is a whole number >= 0 (0: until nothing is deleted), got {max_passes!r}")
+    return int(max_passes)
+
+
+def skeletonize(planes, threshold=0.5, max_passes=0):
+    """Guo-Hall parallel thinning (csrc/skeleton.hip) of the planes binarised as ``planes - threshold > 0`` in fp32 (NaN -> not
+    set; 0.5 on a mask is the project's ``mask > 0.5``): uint8 device tensor [N, H, W] of 0 / 1 for fp32 planes [..., H, W].  A pass is the
+    first sub-iteration followed by the second; the skeleton is the plane after the first pass that deletes nothing, and ``max_passes`` =
+    p > 0 gives the plane after min(p, passes to convergence) passes.  The device runs the passes in groups of up to
+    csbsr_skeleton_max_passes() per launch -- the last group of a ``max_passes`` that is no multiple of it is shorter -- and the host reads
+    the 4-byte count of deleted pixels back once per group, stopping at the first group that deleted nothing."""
+    return _thin(planes, skeleton_threshold(threshold), _skeleton_passes(max_passes))[0]
+
+
+def _thin(planes, t, p_max):
+    """``skeletonize`` on checked arguments: (skeleton, launch groups, passes launched, pixels deleted)"""
+    lib = L.load()
+    x = _dev32(planes)
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    x = x.reshape(-1, H, W)
+    N, dev = x.shape[0], x.device
+    K = int(lib.csbsr_skeleton_max_passes())
+    with torch.cuda.device(dev):
+        st = L.stream(dev)
+        a, b = (torch.empty(N, H, (W + 31) // 32, dtype=torch.int32, device=dev) for _ in range(2))
+        deleted = torch.zeros(1, dtype=torch.int32, device=dev)          # a running total over the groups
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+        L.call("csbsr_skeleton_init", _ptr(x), t, N, H, W, _ptr(a), st)
+        done = total = groups = 0
+        while p_max == 0 or done < p_max:
+            p = K if p_max == 0 else min(K, p_max - done)
+            L.call("csbsr_skeleton_passes", _ptr(a), _ptr(b), N, H, W, p, _ptr(deleted), st)
+            a, b = b, a
+            done, groups = done + p, groups + 1
+            now = int(deleted.item())
+            if now == total:
+                break
+            total = now
+        L.call("csbsr_skeleton_finish", _ptr(a), N, H, W, _ptr(out), st)
+    return out, groups, done, total
+
+
+def centerline_counts(segment_preds, masks, threshold):
+    """The integers of clDice: int32 device tensor [B, 4] = (|S_P|, |S_P & V_L|, |S_L|, |S_L & V_P|) with V_P = segment_preds - threshold > 0
+    (fp32, NaN -> 0), V_L = masks > 0.5, and S_P, S_L their skeletons (``skeletonize``).  Scores: ``cldice_scores``, ``summarize_cldice``."""
+    t = skeleton_threshold(threshold)
+    L.load()
+    p = _dev32(segment_preds)
+    m = _dev32(masks, p)
+    H, W = int(p.shape[-2]), int(p.shape[-1])
+    p, m = p.reshape(-1, H, W), m.reshape(-1, H, W)
+    B = p.shape[0]
+    assert m.shape[0] == B, "one mask per prediction map"
+    sp, sl = skeletonize(p, t), skeletonize(m, 0.5)
+    out = torch.empty(B, 4, dtype=torch.int32, device=p.device)
+    with torch.cuda.device(p.device):
+        L.call("csbsr_centerline_counts", _ptr(sp), _ptr(p), t, _ptr(sl), _ptr(m), B, H, W, _ptr(out), L.stream(p.device))
+    return out
+
+
+def cldice_scores(counts):
+    """(Tprec, Tsens, clDice) float64 [N] from the integer counts [N, 4] of ``centerline_counts``: Tprec = |S_P & V_L| / |S_P|, the part of the
+    predicted centerline inside the ground truth; Tsens = |S_L & V_P| / |S_L|, the part of the ground-truth centerline inside the
+    prediction; clDice their harmonic mean.  The conventions of ``pr_scores``: an empty S_P -> Tprec 1; an empty S_L -> Tsens 1;
+    Tprec + Tsens = 0 -> clDice 0."""
+    c = np.asarray(counts, dtype=np.int64)
+    assert c.ndim == 2 and c.shape[1] == 4, f"counts are [N, 4], got {c.shape}"
+    n_sp, sp_in, n_sl, sl_in = (c[:, i].astype(np.float64) for i in range(4))
+    tp = np.where(n_sp > 0, sp_in / np.maximum(n_sp, 1.0), 1.0)
+    ts = np.where(n_sl > 0, sl_in / np.maximum(n_sl, 1.0), 1.0)
+    cl = np.where(tp + ts > 0, 2.0 * tp * ts / np.where(tp + ts > 0, tp + ts, 1.0), 0.0)
+    return tp, ts, cl
+
+
+def summarize_cldice(counts):
+    """clDice, Tprec, Tsens: the means of the per-image values of ``cldice_scores``; clDice_pooled: the clDice of the counts summed over the
+    images (long cracks weigh more)."""
+    c = np.asarray(counts, dtype=np.int64)
+    assert c.ndim == 2 and c.shape[1] == 4 and c.shape[0] >= 1
+    tp, ts, cl = cldice_scores(c)
+    return {"clDice": float(np.mean(cl)), "Tprec": float(np.mean(tp)), "Tsens": float(np.mean(ts)),
+            "clDice_pooled": float(cldice_scores(c.sum(axis=0, keepdims=True))[2][0])}
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

@@ -640,6 +640,25 @@ int csbsr_surface_gather(const uint8_t* lvl, const uint8_t* gt, const int32_t* d
 int csbsr_pr_sweep(const float* pred, const float* mask, const float* thresholds, int32_t N, int32_t H, int32_t W, int32_t T, int32_t tol2,
                    uint32_t* hist, int32_t* counts, csbsr_stream_t s);
 
+/* Guo-Hall parallel thinning of binary planes on the device and the centerline counts of clDice (csrc/skeleton.hip).
+ * A work plane set is uint32 [N][H][ceil(W / 32)]: one bit per pixel, bit i of word c of a row = pixel x = 32 c + i, the bits past W zero.
+ *   csbsr_skeleton_init   : planes fp32 [N][H][W] -> work, a pixel is set iff  x - threshold > 0  in fp32 (NaN -> not set); the threshold is finite.
+ *   csbsr_skeleton_passes : ``passes`` whole passes (first sub-iteration, then second), 1 <= passes <= csbsr_skeleton_max_passes(), from
+ *                           ``src`` into ``dst`` (two different plane sets: a launch never updates in place).  Adds the number of pixels it
+ *                           deleted to the int32 ``*deleted`` (device memory, one integer atomic per workgroup, every pixel counted by the one
+ *                           workgroup that owns it); the caller zeroes or remembers it.  Passes on a converged plane change nothing.
+ *   csbsr_skeleton_finish : work -> uint8 [N][H][W] of 0 / 1.
+ *   csbsr_centerline_counts: counts int32 [N][4] = (|S_P|, |S_P & V_L|, |S_L|, |S_L & V_P|) with S_P = skel_pred != 0, S_L = skel_gt != 0 (uint8
+ *                           [N][H][W]), V_P = pred - threshold > 0 (fp32, NaN -> 0), V_L = mask > 0.5; the entry zeroes ``counts`` on the stream.
+ * 1 <= H, W <= 8192, N <= 65535.  Integer atomics only: results are run-to-run identical.  No entry synchronises with the host. */
+int32_t csbsr_skeleton_max_passes(void);
+int csbsr_skeleton_init(const float* planes, float threshold, int32_t N, int32_t H, int32_t W, uint32_t* work, csbsr_stream_t s);
+int csbsr_skeleton_passes(const uint32_t* src, uint32_t* dst, int32_t N, int32_t H, int32_t W, int32_t passes, int32_t* deleted,
+                          csbsr_stream_t s);
+int csbsr_skeleton_finish(const uint32_t* work, int32_t N, int32_t H, int32_t W, uint8_t* out, csbsr_stream_t s);
+int csbsr_centerline_counts(const uint8_t* skel_pred, const float* pred, float threshold, const uint8_t* skel_gt, const float* mask, int32_t N,
+                            int32_t H, int32_t W, int32_t* counts, csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
