@@ -179,7 +179,11 @@ SIGNATURES = {
     "csbsr_skeleton_passes": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "csbsr_skeleton_finish": (i32, [vp, i32, i32, i32, vp, vp]),
     "csbsr_centerline_counts": (i32, [vp, vp, f32, vp, vp, i32, i32, i32, vp, vp]),
-    "csbsr_head1_fwd": (i32, [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp]),
+    "csbsr_ccl_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "csbsr_ccl_label": (i32, [vp, f32, i32, i32, i32, i32, vp, vp, vp]),
+    "csbsr_component_sums": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "csbsr_component_keep": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "csbsr_head1_fwd":(i32, [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp]),
     "csbsr_head1_bwd_input": (i32, [vp, i64, vp, i32, vp, i64, i64, vp]),
     "csbsr_adam_step": (i32, [vp, vp, vp, i32, C.c_double, C.c_double, C.c_float, vp]),
     "csbsr_sgd_step": (i32, [vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, vp]),

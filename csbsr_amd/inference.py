@@ -7,7 +7,8 @@ returns the reference's final report, with the saved images and masks leaving th
 (``cldice_threshold``) the centerline Dice of the map at one threshold (csrc/skeleton.hip), neither of which the reference computes.
 ``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
 of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device; on request (``measure_threshold``) with the
-crack's area, centerline length and mean width per image."""
+crack's area, centerline length and mean width per image, and (``min_crack_px``) with the small blobs dropped and the same numbers per
+connected crack (csrc/components.hip)."""
 import csv
 import os
 
@@ -19,6 +20,7 @@ from .data.patch_sampler import JointPatch
 from .engine import _ptr
 from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep, pr_sweep, pr_tol2
 from .utils.estimate_metrics import skeletonize, centerline_counts, cldice_scores, summarize_cldice, unit_threshold
+from .utils.estimate_metrics import label_components, component_min_px, _component_sums, _keep_from_sums, _table_from_sums
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -249,6 +251,48 @@ def write_crack_stats(path, rows):
             w.writerow([name, int(crack), int(skel), repr(float(width))])
 
 
+INSTANCE_COLUMNS = ["name", "crack", "y", "x", "area_px", "length_px", "mean_width_px", "y0", "x0", "y1", "x1"]
+
+
+def crack_instances(table_rows, W):
+    """the ``cracks`` list of one image from its rows of ``component_table`` (plane, label, area_px, skeleton_px, y0, x0, y1, x1), in the
+    table's order = raster order of the first pixel (y, x); length_px is the component's skeleton pixels, a length of 0 gives width 0.0"""
+    out = []
+    for _, label, area, length, y0, x0, y1, x1 in table_rows:
+        y, x = divmod(int(label) - 1, W)
+        out.append(dict(y=y, x=x, area_px=int(area), length_px=int(length), mean_width_px=mean_width(area, length),
+                        bbox=(int(y0), int(x0), int(y1), int(x1))))
+    return out
+
+
+def write_crack_instances(path, rows):
+    """crack_instances.csv: one row per kept crack -- ``rows`` = (name, the image's ``cracks`` list) per image; ``crack`` counts from 0
+    within the image (repr: the shortest text that reads back to the same fp64)"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(INSTANCE_COLUMNS)
+        for name, cracks in rows:
+            for j, c in enumerate(cracks):
+                w.writerow([name, j, c["y"], c["x"], c["area_px"], c["length_px"], repr(float(c["mean_width_px"])), *c["bbox"]])
+
+
+def read_crack_instances(path):
+    """what ``write_crack_instances`` wrote: (name, cracks) per image, in the file's order"""
+    out = []
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != INSTANCE_COLUMNS:
+        raise ValueError(f"{path}: not a crack_instances.csv header: {rows[0]}")
+    for name, j, y, x, area, length, width, y0, x0, y1, x1 in rows[1:]:
+        if not out or out[-1][0] != name:
+            out.append((name, []))
+        if int(j) != len(out[-1][1]):
+            raise ValueError(f"{path}: crack {j} of {name} is out of order")
+        out[-1][1].append(dict(y=int(y), x=int(x), area_px=int(area), length_px=int(length), mean_width_px=float(width),
+                               bbox=(int(y0), int(x0), int(y1), int(x1))))
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -414,7 +458,7 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
 
 # ------------------------------------------------------------------------------------------------ prediction without ground truth
 @torch.no_grad()
-def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None):
+def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -433,12 +477,27 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     map_f32 - t > 0; skeleton_px (int), the size of that region's Guo-Hall skeleton (``skeletonize``) -- the crack's length in pixels --;
     mean_width_px = crack_px / skeleton_px in fp64 (0.0 for an empty skeleton).  The skeleton is taken on the stitched map of the whole
     image, never per tile, and the two integers of all the images of a work unit come back in one read.  With ``save_dir`` it also writes
-    skeletons/<name> (0 / 255) through the ring and, when the generator is exhausted, crack_stats.csv.  None (the default) adds nothing."""
+    skeletons/<name> (0 / 255) through the ring and, when the generator is exhausted, crack_stats.csv.  None (the default) adds nothing.
+
+    ``min_crack_px`` = k, a whole number >= 1 (it needs ``measure_threshold``; anything else is a ValueError before the model runs), measures
+    crack by crack.  With R the region map_f32 - t > 0 and K the pixels of R's 8-connected components of at least k pixels
+    (``label_components``, ``keep_components``): crack_px = |K|; the skeleton is skeletonize(R) & K -- one thinning: two components never
+    share a 3 x 3 neighbourhood, so it is the skeleton of K --; skeleton_px and mean_width_px are taken over K.  New keys: removed_px =
+    |R| - |K|; n_cracks; labels, device int32 [H, W] with the removed components 0; cracks, a list in raster order of the first pixel of
+    dict(y, x, area_px, length_px, mean_width_px, bbox=(y0, x0, y1, x1)) -- (y, x) the first pixel, length_px the crack's skeleton pixels, the
+    box inclusive (``crack_instances``).  The integers of a unit still come back in one read, the unit's tables in one more.  With
+    ``save_dir``, skeletons/<name> shows the kept skeleton, crack_stats.csv holds the values over K, and crack_instances.csv
+    (``write_crack_instances``) is written when the generator is exhausted.  None (the default) adds nothing."""
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
+    min_px = None
+    if min_crack_px is not None:
+        if measure is None:
+            raise ValueError("min_crack_px filters what measure_threshold measures: give measure_threshold too")
+        min_px = component_min_px(min_crack_px, "min_crack_px")
     saver = None
     if save_dir is not None:
         saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
-    stats = []
+    stats, instances = [], []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -461,16 +520,30 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         kernels = torch.cat(kernels)
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
-        extra, px = [], None
+        extra, px, kept_labels, tables = [], None, [], None
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
-            px = []
-            for o, H, W, _, _ in layout:                     # one plane per image: the stitched map, never a tile
-                sk = skeletonize(map_f32[o:o + H * W].view(1, H, W), measure).view(-1)
+            px, tables = [], []
+            for j, (o, H, W, _, _) in enumerate(layout):     # one plane per image: the stitched map, never a tile
+                plane = map_f32[o:o + H * W].view(1, H, W)
+                sk = skeletonize(plane, measure).view(-1)
+                if min_px is None:
+                    skel_u8[o:o + H * W] = sk * 255
+                    px.append(torch.stack([(map_f32[o:o + H * W] - t32 > 0).sum(), sk.sum()]))
+                    continue
+                labels = label_components(plane, measure)
+                acc = _component_sums(labels, sk)
+                keep, kept = _keep_from_sums(labels, acc, min_px, want_labels=True)
+                sk = sk * keep.view(-1)                      # skeleton(R) & K = skeleton(K)
                 skel_u8[o:o + H * W] = sk * 255
-                px.append(torch.stack([(map_f32[o:o + H * W] - t32 > 0).sum(), sk.sum()]))
+                table = _table_from_sums(labels, acc, min_px)
+                table[:, 0] = j                              # the image within the unit
+                tables.append(table)
+                kept_labels.append(kept.view(H, W))
+                px.append(torch.stack([keep.sum(), sk.sum(), (labels != 0).sum()]))
             px = torch.stack(px).cpu().tolist()              # the unit's integers in one read
+            tables = torch.cat(tables).cpu().numpy() if min_px is not None else None         # and the unit's tables in one more
             extra = [skel_u8]
         if saver is not None:
             planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
@@ -483,8 +556,14 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 crack, skel = int(px[j][0]), int(px[j][1])
                 item.update(crack_px=crack, skeleton_px=skel, mean_width_px=mean_width(crack, skel))
                 stats.append((loader.names[i], crack, skel, item["mean_width_px"]))
+                if min_px is not None:
+                    cracks = crack_instances(tables[tables[:, 0] == j].tolist(), W)
+                    item.update(removed_px=int(px[j][2]) - crack, n_cracks=len(cracks), labels=kept_labels[j], cracks=cracks)
+                    instances.append((loader.names[i], cracks))
             yield item
     if saver is not None:
         saver.drain()
         if measure is not None:
             write_crack_stats(os.path.join(save_dir, "crack_stats.csv"), stats)
+        if min_px is not None:
+            write_crack_instances(os.path.join(save_dir, "crack_instances.csv"), instances)

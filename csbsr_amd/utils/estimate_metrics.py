@@ -203,6 +203,102 @@ def summarize_cldice(counts):
             "clDice_pooled": float(cldice_scores(c.sum(axis=0, keepdims=True))[2][0])}
 
 
+# ------------------------------------------------------------------------------------------- connected components
+CC_ACC = 5                                                   # csrc/components.hip: area_px, skeleton_px, x0, y1, x1 per root pixel
+TABLE_COLUMNS = ("plane", "label", "area_px", "skeleton_px", "y0", "x0", "y1", "x1")
+
+
+def component_min_px(min_px, what="min_px"):
+    """the smallest component that is kept, in pixels: a whole number >= 1 (Python or NumPy, not a bool), anything else is a ValueError"""
+    if isinstance(min_px, (bool, np.bool_)) or not isinstance(min_px, (int, np.integer)) or min_px < 1:
+        raise ValueError(f"{what} is a whole number >= 1, got {min_px!r}")
+    return int(min_px)
+
+
+def _connectivity(connectivity):
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError(f"connectivity is 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def label_components(planes, threshold=0.5, connectivity=8):
+    """Connected components (csrc/components.hip) of the planes binarised as ``planes - threshold > 0`` in fp32 (NaN -> not set, the rule of
+    ``skeletonize``): int32 device tensor [N, H, W] for fp32 planes [..., H, W].  A background pixel is 0, a set pixel 1 + min(y W + x) over
+    its 4- or 8-connected component -- 1 + the linear index of the component's first pixel in raster order.  Planes are independent; the
+    value is defined by a minimum, so two runs give the same bits."""
+    t, conn = skeleton_threshold(threshold), _connectivity(connectivity)
+    L.load()
+    x = _dev32(planes)
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    x = x.reshape(-1, H, W)
+    N, dev = x.shape[0], x.device
+    work, labels = (torch.empty(N, H, W, dtype=torch.int32, device=dev) for _ in range(2))
+    with torch.cuda.device(dev):
+        L.call("csbsr_ccl_label", _ptr(x), t, N, H, W, conn, _ptr(work), _ptr(labels), L.stream(dev))
+    return labels
+
+
+def _labels(labels):
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int32 and labels.dim() == 3):
+        raise ValueError("labels is the int32 device tensor [N, H, W] of label_components")
+    return labels.contiguous()
+
+
+def _component_sums(labels, skeleton=None):
+    """the accumulators of csbsr_component_sums, int32 [N, 5, H * W]: only the slots of root pixels hold values"""
+    N, H, W = labels.shape
+    sk = None
+    if skeleton is not None:
+        if not (torch.is_tensor(skeleton) and skeleton.dtype == torch.uint8 and skeleton.numel() == labels.numel()):
+            raise ValueError("skeleton is a uint8 tensor with one value per label")
+        sk = skeleton.to(labels.device).contiguous()
+    acc = torch.empty(N, CC_ACC, H * W, dtype=torch.int32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        L.call("csbsr_component_sums", _ptr(labels), None if sk is None else _ptr(sk), N, H, W, _ptr(acc), L.stream(labels.device))
+    return acc
+
+
+def _table_from_sums(labels, acc, min_px):
+    """the rows of ``component_table`` from the accumulators: the roots are the pixels that carry their own index + 1, and torch.nonzero
+    returns them in raster order, plane by plane -- sorted by (plane, label)"""
+    N, H, W = labels.shape
+    flat = labels.view(N, H * W)
+    roots = torch.nonzero(flat == torch.arange(1, H * W + 1, dtype=torch.int32, device=labels.device))
+    n, i = roots[:, 0], roots[:, 1]
+    v = acc[n, :, i]                                         # [M, 5]
+    rows = torch.stack([n, i + 1, v[:, 0], v[:, 1], torch.div(i, W, rounding_mode="floor"), v[:, 2], v[:, 3], v[:, 4]], 1).to(torch.int32)
+    return rows[rows[:, 2] >= min_px] if min_px > 1 else rows
+
+
+def component_table(labels, skeleton=None, min_px=1):
+    """One row per component of ``label_components``' labels with at least ``min_px`` pixels: int32 device tensor [M, 8] with the columns
+    (plane, label, area_px, skeleton_px, y0, x0, y1, x1), sorted by (plane, label).  The box is inclusive; ``skeleton`` (uint8 [N, H, W],
+    e.g. ``skeletonize``'s) gives skeleton_px = its non-zero pixels inside the component -- the crack's length --, 0 without one."""
+    k = component_min_px(min_px)
+    L.load()
+    labels = _labels(labels)
+    return _table_from_sums(labels, _component_sums(labels, skeleton), k)
+
+
+def _keep_from_sums(labels, acc, min_px, want_labels=False):
+    N, H, W = labels.shape
+    keep = torch.empty(N, H, W, dtype=torch.uint8, device=labels.device)
+    kept = torch.empty_like(labels) if want_labels else None
+    with torch.cuda.device(labels.device):
+        L.call("csbsr_component_keep", _ptr(labels), _ptr(acc), N, H, W, min_px, _ptr(keep), None if kept is None else _ptr(kept),
+               L.stream(labels.device))
+    return keep, kept
+
+
+def keep_components(labels, min_px):
+    """uint8 device tensor [N, H, W]: 1 where the pixel belongs to a component of at least ``min_px`` pixels, else 0 (the speckle filter;
+    min_px = 1 keeps every set pixel)."""
+    k = component_min_px(min_px)
+    L.load()
+    labels = _labels(labels)
+    return _keep_from_sums(labels, _component_sums(labels), k)[0]
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

@@ -659,6 +659,29 @@ int csbsr_skeleton_finish(const uint32_t* work, int32_t N, int32_t H, int32_t W,
 int csbsr_centerline_counts(const uint8_t* skel_pred, const float* pred, float threshold, const uint8_t* skel_gt, const float* mask, int32_t N,
                             int32_t H, int32_t W, int32_t* counts, csbsr_stream_t s);
 
+/* Connected components of binary planes on the device, per-component sums and the small-component filter (csrc/components.hip).
+ *   csbsr_ccl_label      : planes fp32 [N][H][W], a pixel is set iff  x - threshold > 0  in fp32 (NaN -> not set; the threshold is finite);
+ *                          connectivity 4 or 8.  labels int32 [N][H][W]: 0 for background, 1 + min(y W + x) over its component for a set pixel
+ *                          -- 1 + the linear index of the component's first pixel in raster order; planes are independent.  work: int32
+ *                          [N][H][W] scratch (the parent forest), another array than labels.  Three launches (tile-local labelling, one merge
+ *                          of all tile seams, flatten); the value is defined by a minimum, so the bits do not depend on scheduling.
+ *   csbsr_ccl_tile       : the tile of the local labelling, rows and columns (the seams lie at multiples of them).
+ *   csbsr_component_sums : labels as above; skeleton uint8 [N][H][W] (!= 0: a skeleton pixel) or NULL.  acc int32 [N][5][H W], indexed by ROOT
+ *                          pixel i = label - 1: acc[n][0][i] = area_px, [1] = skeleton_px (skeleton pixels inside the component; 0 without a
+ *                          skeleton), [2] = x0 (min x), [3] = y1 (max y), [4] = x1 (max x); y0 is the root's own row i / W.  Scratch size:
+ *                          5 int32 per pixel; ONLY the slots of root pixels are written, the others are left as they were.
+ *   csbsr_component_keep : keep uint8 [N][H][W] = 1 where the pixel's component has >= min_px pixels (acc of csbsr_component_sums), else 0;
+ *                          labels_out (int32 [N][H][W] or NULL, may be labels itself): the labels with the other components zeroed.
+ * 1 <= H, W <= 8192 (every index and count fits an int32), 1 <= N <= 65535, min_px >= 1; a null pointer, a size outside these, another
+ * connectivity or a min_px < 1 is refused (non-zero return) before anything is launched.  Integer atomics only: results are run-to-run
+ * identical.  No entry synchronises with the host. */
+int csbsr_ccl_tile(int32_t* th, int32_t* tw);
+int csbsr_ccl_label(const float* planes, float threshold, int32_t N, int32_t H, int32_t W, int32_t connectivity, int32_t* work,
+                    int32_t* labels, csbsr_stream_t s);
+int csbsr_component_sums(const int32_t* labels, const uint8_t* skeleton, int32_t N, int32_t H, int32_t W, int32_t* acc, csbsr_stream_t s);
+int csbsr_component_keep(const int32_t* labels, const int32_t* acc, int32_t N, int32_t H, int32_t W, int32_t min_px, uint8_t* keep,
+                         int32_t* labels_out, csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
