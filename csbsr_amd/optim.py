@@ -50,6 +50,14 @@ def _check(p, g, dev, who):
         raise L.CsbsrHipError(f"csbsr_amd.optim.{who}: contiguous fp32 parameters and gradients on one device only")
 
 
+def _check_aligned(i, **tensors):
+    """csbsr_adam_step moves float4s and its table has no ``vec`` flag (csbsr_hip.h): a view that starts inside an allocation is refused"""
+    for name, t in tensors.items():
+        if t is not None and t.data_ptr() % 16 != 0:
+            raise L.CsbsrHipError(f"csbsr_amd.optim.Adam: {name} of parameter {i} (shape {tuple(t.shape)}) is not 16-byte aligned "
+                                  f"(a view that starts inside an allocation?): csbsr_adam_step needs 16-byte aligned p, g, exp_avg and exp_avg_sq")
+
+
 class Adam(_MultiTensor):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
@@ -70,6 +78,9 @@ class Adam(_MultiTensor):
             lr = float(group["lr"])
             dev = ps[0].device
             tab = np.zeros(len(ps), dtype=_DT)
+            for i, p in enumerate(ps):          # (before any state is created or a step count advances: a refused step changes nothing)
+                st = self.state.get(p, {})
+                _check_aligned(i, p=p, grad=p.grad, exp_avg=st.get("exp_avg"), exp_avg_sq=st.get("exp_avg_sq"))
             for i, p in enumerate(ps):
                 g = p.grad
                 _check(p, g, dev, "Adam")

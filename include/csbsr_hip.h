@@ -296,7 +296,10 @@ int csbsr_set_reduction_scratch(float* buf, int64_t elems);
  * LIST of fp32 tensors in one launch: m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g; p -= step_size m / (sqrt(v) / bc2_sqrt + eps), with
  * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) per tensor (a parameter whose gradient was None in some step has a smaller t,
  * exactly like torch's per-parameter state["step"]).  ``tensors`` (device memory): the table; ``block_tensor`` / ``block_chunk`` (device, int32
- * [nblocks]): workgroup b updates elements [8192 block_chunk[b], 8192 (block_chunk[b] + 1)) of tensor block_tensor[b]. */
+ * [nblocks]): workgroup b updates elements [8192 block_chunk[b], 8192 (block_chunk[b] + 1)) of tensor block_tensor[b]; a chunk that
+ * starts at or past the tensor's end touches nothing, and nblocks == 0 launches nothing.  p, g, m and v MUST be 16-byte aligned: the
+ * kernel moves float4s and this table has no ``vec`` flag (csbsr_sgd_tensor_t has one); csbsr_amd.optim.Adam refuses any other tensor
+ * before it touches its state. */
 typedef struct {
   float* p; const float* g; float* m; float* v;
   int64_t n;

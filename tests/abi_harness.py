@@ -1,11 +1,12 @@
 """Calling the library's C entry points from a test with every buffer guarded (a plain helper module: tests/test_metrics_exact_gpu.py,
-tests/test_image_exact_gpu.py and tests/test_elementwise_exact_gpu.py import it).
+tests/test_image_exact_gpu.py, tests/test_elementwise_exact_gpu.py and tests/test_step_tail_exact_gpu.py import it).
 
 Every row: the shared reduction scratch is refilled with NaN before the call (a fold that reads a slot nobody wrote turns the result
 into NaN); every input sits inside a NaN-filled allocation (a read outside the slice poisons the result instead of faulting); every
 output sits inside a sentinel-filled allocation whose two margins are checked afterwards (In16 / Out16: fp16 NHWC maps, whole or as a
-channel slice of a wider buffer whose other channels are guarded the same way); the call runs twice and the two results
-must be bit-identical.
+channel slice of a wider buffer whose other channels are guarded the same way; In16Split: the two planes of a split map in one such
+allocation); a table of structs or an index array sits inside an 0xFF-filled allocation and is compared byte for byte afterwards
+(Raw); the call runs twice and the two results must be bit-identical.
 """
 import ctypes as C
 
@@ -60,6 +61,53 @@ class In16:
     @property
     def ptr(self):
         return C.c_void_p(self.v.data_ptr())
+
+
+class In16Split:
+    """the two planes of a split map (hi + lo, both [npix, c] fp16-exact) in the layout of In16, inside ONE NaN-filled allocation with a
+    NaN gap between them; ``lo`` is the distance of the planes in halves, as the split entry points take it"""
+
+    def __init__(self, hi, lo, ld=None, c0=0):
+        hi, lo = (torch.as_tensor(np.ascontiguousarray(a)) for a in (hi, lo))
+        assert hi.dim() == 2 and hi.shape == lo.shape, "In16Split takes two [npix, c]"
+        self.npix, self.c = hi.shape
+        self.ld = self.c if ld is None else ld
+        assert self.ld % 8 == 0 and c0 % 8 == 0 and c0 + self.c <= self.ld
+        plane = self.npix * self.ld
+        self.lo = plane + PAD
+        self.buf = torch.full((2 * plane + 3 * PAD,), float("nan"), dtype=torch.float16, device=_dev())
+        for k, x in enumerate((hi, lo)):
+            h = x.to(torch.float16)
+            assert torch.equal(h.double(), x.double()), "In16Split: the values are not fp16-exact"
+            v = self.buf[PAD + k * self.lo:PAD + k * self.lo + plane].view(self.npix, self.ld)[:, c0:c0 + self.c]
+            v.copy_(h)
+            if k == 0:
+                self.v = v
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.v.data_ptr())
+
+
+class Raw:
+    """device copy of a host array's BYTES (a table of structs, an index array) in the middle of an allocation filled with 0xFF (NaN as a
+    float, -1 as an index), 256 bytes either side; unchanged(): the device still holds exactly these bytes, margins included"""
+
+    def __init__(self, arr):
+        self.host = torch.from_numpy(np.frombuffer(np.ascontiguousarray(arr).tobytes(), dtype=np.uint8).copy())
+        n = self.host.numel()
+        self.buf = torch.full((n + 512,), 0xFF, dtype=torch.uint8, device=_dev())
+        self.v = self.buf[256:256 + n]
+        self.v.copy_(self.host)
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.v.data_ptr())
+
+    def unchanged(self):
+        b = self.buf.cpu()
+        n = self.host.numel()
+        return bool(torch.equal(b[256:256 + n], self.host) and (b[:256] == 0xFF).all() and (b[256 + n:] == 0xFF).all())
 
 
 class Out16:
