@@ -166,13 +166,10 @@ REQUIRED_VARIANTS = {
 ROW_ENTRY = {"fwd": "Conv.fwd", "dgrad": "Conv.bwd_input", "wgrad": "Conv.bwd_weights", "classbias": "Conv.fwd_classbias"}
 # (the rows of tests/fused_exact_cases.py -- the paths with second outputs, the folded segment, ShuffleConv, kp_bwd -- name their entry
 # point themselves: FRow.entry; tests/test_conv_exact_coverage_cpu.py counts both tables)
-REQUIRED_MODES = ("sigmoid", "split")
+# (the split-precision rows -- the fused-split instances of conv_igemm_glds.hip, fwd_blocks 1 / 2 / 3, split output slices, the split-input
+# forms of Conv.fwd_folded / fwd_const_1x1, the high-precision dgrad -- are a third table with a lattice of its own,
+# tests/split_conv_cases.py; each of its rows names its mode, "split" or "Conv.hp_dgrad")
+REQUIRED_MODES = ("sigmoid", "split", "Conv.hp_dgrad")
 
-_SPLIT = ("split-precision (hi + lo) operands need a lattice reference of their own -- x_lo planes, the round-to-nearest weight split, "
-          "WSCALE, the hi + lo output pair -- which this table does not build yet: a follow-up")
-NOT_COVERED = {
-    "GLDS64/1": _SPLIT, "GLDS64/3": _SPLIT, "GLDS128/1": _SPLIT, "GLDS128/3": _SPLIT,
-    "GLDS256/1": _SPLIT, "GLDS256/3": _SPLIT, "GLDS256W/1": _SPLIT, "GLDS256W/3": _SPLIT,
-    "split": _SPLIT + " (fwd_blocks 1 / 2 / 3, split output slices, Conv._wq / Conv._dc_bias on exact weights, and the split-input forms of "
-                      "Conv.fwd_folded and Conv.fwd_const_1x1, whose plain-input forms have rows in tests/fused_exact_cases.py)",
-}
+# required paths with neither a row nor a test yet, and why (nothing at present)
+NOT_COVERED = {}

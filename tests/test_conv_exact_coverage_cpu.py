@@ -3,8 +3,8 @@ the weight-gradient kernel IDs (``enum WGRADK_*``, csrc/conv_wgrad.h) are parsed
 of tests/conv_exact_cases.py -- or be listed in its EXCLUDED with a reason.  A new kernel therefore arrives with an exact test.  The same
 holds for the template instances the dispatchers build (REQUIRED_VARIANTS), the engine's entry points into the kernels (Conv's fwd* /
 bwd* methods and subclasses, read from csbsr_amd/engine.py; the public functions of csbsr_amd/modeling/kp_bwd.py other than its ``*_ok``
-predicates) and the sigmoid / split operand modes: each has a row -- here or in tests/fused_exact_cases.py, whose rows name their entry
-point -- or a NOT_COVERED reason, so what the tables leave out is written down next to them.  The debug-mode defaults the GPU test restores are checked against
+predicates) and the sigmoid / split / high-precision-dgrad operand modes: each has a row -- here, in tests/fused_exact_cases.py or in
+tests/split_conv_cases.py (the split-fp16 paths), whose rows name their entry point -- or a NOT_COVERED reason, so what the tables leave out is written down next to them.  The debug-mode defaults the GPU test restores are checked against
 the sources' initial values."""
 import os
 import re
@@ -13,6 +13,7 @@ import pytest
 
 from conv_exact_cases import DEFAULT_MODES, EXCLUDED, NOT_COVERED, REQUIRED_MODES, REQUIRED_VARIANTS, ROW_ENTRY, ROWS
 from fused_exact_cases import FUSED_ROWS
+from split_conv_cases import SPLIT_ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "csbsr_amd", "csrc")
@@ -79,24 +80,26 @@ def entry_points():
     return meths + subs + kp
 
 
-def _instances(rows, fused):
-    """(kernel ID, template instance) pairs the rows of both tables assert"""
-    return {(r.kid, r.var) for r in rows if r.op != "wgrad"} | {(r.kid, r.var) for r in fused if isinstance(r.kid, int)}
+def _instances(rows, fused, split=SPLIT_ROWS):
+    """(kernel ID, template instance) pairs the rows of the three tables assert"""
+    return ({(r.kid, r.var) for r in rows if r.op != "wgrad"} | {(r.kid, r.var) for r in fused if isinstance(r.kid, int)}
+            | {(r.kid, r.var) for r in split})
 
 
-def missing_paths(rows, not_covered, fused=FUSED_ROWS):
+def missing_paths(rows, not_covered, fused=FUSED_ROWS, split=SPLIT_ROWS):
     """the template instances (REQUIRED_VARIANTS), entry points and operand modes with neither a row nor a NOT_COVERED reason"""
-    have = _instances(rows, fused)
+    have = _instances(rows, fused, split)
     miss = []
     for fam, (kid, vars_) in REQUIRED_VARIANTS.items():
         for v in vars_:
             if (kid, v) not in have and f"{fam}/{v}" not in not_covered:
                 miss.append(f"{fam}/{v}")
+    # (a split row covers its instance and its mode, not its entry point: the plain-operand row of that entry point stays required)
     ops = {ROW_ENTRY[r.op] for r in rows} | {r.entry for r in fused}
     for ep in entry_points():
         if ep not in ops and ep not in not_covered:
             miss.append(ep)
-    epis = {m for r in rows for m in r.epi.split("_")}
+    epis = {m for r in rows for m in r.epi.split("_")} | {r.mode for r in split}
     for m in REQUIRED_MODES:
         if m not in epis and m not in not_covered:
             miss.append(m)
@@ -119,15 +122,26 @@ def test_not_covered_is_current():
             kid, vars_ = REQUIRED_VARIANTS[fam]
             assert int(v) in vars_ and (kid, int(v)) not in have, f"NOT_COVERED[{name}]: not a required instance, or it has a row"
         elif name in REQUIRED_MODES:
-            assert name not in {m for r in ROWS for m in r.epi.split("_")}, f"NOT_COVERED[{name}] has a row"
+            assert name not in {m for r in ROWS for m in r.epi.split("_")} | {r.mode for r in SPLIT_ROWS}, f"NOT_COVERED[{name}] has a row"
         else:
             assert name in eps and name not in {ROW_ENTRY[r.op] for r in ROWS} | {r.entry for r in FUSED_ROWS}, \
                 f"NOT_COVERED[{name}]: no such entry point, or it has a row"
 
 
-def test_not_covered_is_down_to_the_split_precision_entries():
-    assert set(NOT_COVERED) == {f"{fam}/{v}" for fam in ("GLDS64", "GLDS128", "GLDS256", "GLDS256W") for v in (1, 3)} | {"split"}
-    assert "fwd_folded" in NOT_COVERED["split"] and "fwd_const_1x1" in NOT_COVERED["split"]
+SPLIT_INSTANCES = [f"{fam}/{v}" for fam in ("GLDS64", "GLDS128", "GLDS256", "GLDS256W") for v in (1, 3)]
+
+
+def test_nothing_is_left_uncovered():
+    """the split-precision entries were the last ones: every fused-split instance, the split mode and the high-precision dgrad have rows in
+    tests/split_conv_cases.py, and it is those rows that cover them"""
+    assert NOT_COVERED == {}
+    assert missing_paths(ROWS, NOT_COVERED, split=[]) == SPLIT_INSTANCES + ["split", "Conv.hp_dgrad"]
+    entries = {r.entry for r in SPLIT_ROWS}
+    assert {"Conv.fwd", "Conv.fwd_folded", "Conv.fwd_const_1x1", "Conv.bwd_input"} <= entries
+    fwd = [r for r in SPLIT_ROWS if r.mode == "split"]
+    assert {r.blocks for r in fwd} == {1, 2, 3} and {r.plan for r in fwd} == {1, 2, 3, 4, 5} and {r.fused for r in fwd} == {0, 1}
+    assert any(len(r.out_c0) > 1 and r.mode == "split" for r in SPLIT_ROWS), "no split output slice row"
+    assert any(r.epi == "bn" for r in fwd) and any(r.epi.endswith("_fma") for r in fwd)
 
 
 def test_fused_rows_name_real_entry_points():
@@ -138,10 +152,11 @@ def test_fused_rows_name_real_entry_points():
 
 def test_the_path_check_names_what_is_missing():
     """dropping a row, a reason, or a new Conv method shows up by name"""
-    assert missing_paths([r for r in ROWS if r.name != "x3n_narrow_bn"], NOT_COVERED) == ["X3N/3"]
-    nc = dict(NOT_COVERED)
-    del nc["split"]
-    assert missing_paths(ROWS, nc) == ["split"]
+    assert missing_paths([r for r in ROWS if r.name != "x3n_narrow_bn"], NOT_COVERED, split=[r for r in SPLIT_ROWS if r.name != "fs2_x3n_bn"]) == ["X3N/3"]
+    assert missing_paths(ROWS, NOT_COVERED, split=[r for r in SPLIT_ROWS if r.mode != "split"]) == SPLIT_INSTANCES + ["split"]
+    assert missing_paths(ROWS, NOT_COVERED, split=[r for r in SPLIT_ROWS if r.mode != "Conv.hp_dgrad"]) == ["Conv.hp_dgrad"]
+    assert missing_paths(ROWS, NOT_COVERED, split=[r for r in SPLIT_ROWS if r.name != "fs_glds256w_gk"]) == ["GLDS256W/3"]
+    assert missing_paths(ROWS, {"split": "a reason"}, split=[r for r in SPLIT_ROWS if r.mode != "split"]) == SPLIT_INSTANCES
     assert "Conv.fwd_classbias" in entry_points() and "Conv.bwd_weights_folded" in entry_points()
     # ... and so does dropping the rows of the second table, or one of them, or a new public function of kp_bwd.py
     assert missing_paths(ROWS, NOT_COVERED, fused=[]) == ["TP/14", "TP/13", "Conv.fwd_folded", "Conv.fwd_const_1x1", "Conv.bwd_weights_folded",
