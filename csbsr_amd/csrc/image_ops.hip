@@ -1180,9 +1180,13 @@ extern "C" int csbsr_head1_bwd_input(const void* dpre, int64_t dpre_ld, const fl
 }
 
 // ------------------------------------------------------------------------------------------- exact EDT / SDF
-// Squared Euclidean distance to the nearest zero pixel of `img` (distance_transform_edt semantics) by the exact
-// two-pass method: (1) per column, nearest zero above/below (1-D scan); (2) per row, lower envelope of parabolas
-// evaluated by brute force over the row held in LDS (W <= 4096).  inv = 1 computes it for the complement.
+// Squared Euclidean distance to the nearest background pixel (distance_transform_edt semantics) by the exact two-pass method: (1) per
+// column, nearest background pixel above/below (1-D scan); (2) per row, lower envelope of parabolas over the row held in LDS (the entry
+// points accept W <= 8192).  inv = 1 computes it for the complement.
+// The foreground rule of csbsr_sdf and csbsr_crack_weight is the reference's ``img_gt.astype(np.uint8)`` (compute_sdf1_1,
+// CrackOrientedExpWeight): a pixel is foreground when its value TRUNCATED TO uint8 is non-zero.  0.5, 0.99, a denormal and -0.0 are
+// background, 1.0, 1.5 and 254.9 foreground; mask values in [0, 256).
+__device__ __forceinline__ bool mask_fg(float v) { return (unsigned char)(int)v != 0; }
 __global__ void edt_cols_kernel(const float* mask, float* g, int N, int H, int W, int inv) {
   const long total = (long)N * W;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -1192,21 +1196,25 @@ __global__ void edt_cols_kernel(const float* mask, float* g, int N, int H, int W
     const float BIG = 1e9f;
     float d = BIG;
     for (int y = 0; y < H; ++y) {
-      const bool fg = (mp[(long)y * W] != 0.f) != (inv != 0);
+      const bool fg = mask_fg(mp[(long)y * W]) != (inv != 0);
       d = fg ? d + 1.f : 0.f;
       gp[(long)y * W] = d;
     }
     d = BIG;
     for (int y = H - 1; y >= 0; --y) {
-      const bool fg = (mp[(long)y * W] != 0.f) != (inv != 0);
+      const bool fg = mask_fg(mp[(long)y * W]) != (inv != 0);
       d = fg ? d + 1.f : 0.f;
       const float cur = gp[(long)y * W];
       gp[(long)y * W] = cur < d ? cur : d;
     }
   }
 }
-// Row pass of the exact EDT: dist(x) = sqrt(min over x' of g(x')^2 + (x - x')^2), g = the column pass's vertical distance.  Every sum is an
-// integer below 2^24, so the minimum is exact whatever the search order.  Round 6: the search goes block by block (32 columns) with the
+// Row pass of the exact EDT: dist(x) = sqrt(min over x' of g(x')^2 + (x - x')^2), g = the column pass's vertical distance.  Exactness
+// domain: while H^2 + W^2 < 2^24 every square and every sum is an integer below 2^24, the minimum is exact whatever the search order and
+// dist is the correctly rounded root of the exact squared distance.  Beyond it (W > 4095, up to the accepted 8192) the squares (x - x')^2
+// and the sums round to fp32: the search is still sound (rounding is monotone, so a block's rounded lower bound never exceeds a rounded
+// candidate of that block) and returns the minimum of the ROUNDED sums, within 2 * 2^-24 relative of the exact squared distance -- one ulp
+// effects on dist, no more.  The search goes block by block (32 columns) with the
 // block minima of g^2 as lower bounds -- a block whose bound  bmin + gap^2  cannot beat the best candidate so far is skipped -- instead of
 // expanding column by column until r^2 >= best: with the sparse crack masks of full-size images (0.4 % foreground, nearest crack hundreds of
 // pixels away) the column-by-column form cost 5.8 ms per config-2 step (1.5 ms on the periodic masks of the earlier bench data).
@@ -1259,8 +1267,8 @@ __global__ __launch_bounds__(256) void edt_rows_kernel(const float* g, float* di
     atomicMax(reinterpret_cast<int*>(minmax + (row / H)), __float_as_int(mx));   // non-negative floats order as ints
   }
 }
-// sdf = negdis/max(negdis) - posdis/max(posdis), inner boundary -> 0, all-background sample -> 0
-// (min of each distance map is 0 whenever the mask has both classes; compute_sdf1_1 only runs if posmask.any())
+// sdf = negdis/max(negdis) - posdis/max(posdis), inner boundary (mask_fg pixels with a background 4-neighbour) -> 0, all-background
+// sample -> 0 (min of each distance map is 0 whenever the mask has both classes; compute_sdf1_1 only runs if posmask.any())
 __global__ void sdf_combine_kernel(const float* mask, const float* posdis, const float* negdis, const float* pmax, const float* nmax,
                                    float* sdf, int N, int H, int W) {
   const long total = (long)N * H * W;
@@ -1271,13 +1279,14 @@ __global__ void sdf_combine_kernel(const float* mask, const float* posdis, const
     float v = 0.f;
     if (pm > 0.f) {     // posmask.any()
       const float* mp = mask + n * H * W;
-      const bool fg = mp[(long)y * W + x] != 0.f;
-      // nm == 0: mask is all foreground -> negdis == 0 everywhere and the reference divides 0/0 (NaN); mirror with 0
+      const bool fg = mask_fg(mp[(long)y * W + x]);
+      // nm == 0: mask is all foreground -> negdis == 0 everywhere and the reference divides 0/0 (NaN); the outside term is 0 instead, and
+      // the inside term is 1 everywhere (no background pixel: every posdis is the row pass's 1e9 and so is its maximum): sdf = -1
       const float nterm = nm > 0.f ? negdis[i] / nm : 0.f;
       v = nterm - posdis[i] / pm;
       if (fg) {
-        const bool up = mp[(long)(y > 0 ? y - 1 : y) * W + x] != 0.f, dn = mp[(long)(y < H - 1 ? y + 1 : y) * W + x] != 0.f;
-        const bool lf = mp[(long)y * W + (x > 0 ? x - 1 : x)] != 0.f, rt = mp[(long)y * W + (x < W - 1 ? x + 1 : x)] != 0.f;
+        const bool up = mask_fg(mp[(long)(y > 0 ? y - 1 : y) * W + x]), dn = mask_fg(mp[(long)(y < H - 1 ? y + 1 : y) * W + x]);
+        const bool lf = mask_fg(mp[(long)y * W + (x > 0 ? x - 1 : x)]), rt = mask_fg(mp[(long)y * W + (x < W - 1 ? x + 1 : x)]);
         if (!(up && dn && lf && rt)) v = 0.f;
       }
     }
@@ -1303,9 +1312,9 @@ extern "C" int csbsr_sdf(const float* mask, float* sdf, float* scratch /*3*N*H*W
 
 // ------------------------------------------------------------------------------------------- crack-oriented weight
 // w^C = lambda * exp(-amp * d), d = exact Euclidean distance to the nearest crack pixel (CrackOrientedExpWeight, oriented_weight.py:46-58,
-// 92-119).  Column pass of its own: a pixel is foreground when the mask value TRUNCATED TO uint8 is non-zero (the reference's
-// astype(np.uint8): 0.5 and 0.99 are background; mask values in [0, 256)), not csbsr_sdf's ``!= 0``; g = vertical distance to the nearest
-// foreground pixel of the column, 1e9 when the column has none.
+// 92-119).  Column pass of its own with csbsr_sdf's foreground rule (mask_fg: the mask value TRUNCATED TO uint8 is non-zero, the
+// reference's astype(np.uint8): 0.5 and 0.99 are background; mask values in [0, 256)); g = vertical distance to the nearest foreground
+// pixel of the column, 1e9 when the column has none.
 __global__ void crack_cols_kernel(const float* mask, float* g, int N, int H, int W) {
   const long total = (long)N * W;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -1315,20 +1324,21 @@ __global__ void crack_cols_kernel(const float* mask, float* g, int N, int H, int
     const float BIG = 1e9f;
     float d = BIG;
     for (int y = 0; y < H; ++y) {
-      const bool fg = (unsigned char)(int)mp[(long)y * W] != 0;
+      const bool fg = mask_fg(mp[(long)y * W]);
       d = fg ? 0.f : d + 1.f;
       gp[(long)y * W] = d;
     }
     d = BIG;
     for (int y = H - 1; y >= 0; --y) {
-      const bool fg = (unsigned char)(int)mp[(long)y * W] != 0;
+      const bool fg = mask_fg(mp[(long)y * W]);
       d = fg ? 0.f : d + 1.f;
       const float cur = gp[(long)y * W];
       gp[(long)y * W] = cur < d ? cur : d;
     }
   }
 }
-// Row pass: edt_rows_kernel's exact block-bounded search (squares in LDS, 32-column block minima as lower bounds) with the weight as its
+// Row pass: edt_rows_kernel's block-bounded search (squares in LDS, 32-column block minima as lower bounds; the same copy of the loop, so
+// the same exactness domain H^2 + W^2 < 2^24 and the same accepted width) with the weight as its
 // epilogue -- the distance goes from the register into expf and only w is written.  A row whose every column is 1e9 belongs to a sample
 // without a foreground pixel (each g column spans the whole image): the reference leaves that sample's distance map at zero, w = lambda.
 __global__ __launch_bounds__(256) void crack_rows_weight_kernel(const float* g, float* w, int W, float namp, float lambda) {

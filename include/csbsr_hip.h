@@ -518,7 +518,11 @@ int csbsr_blur_bwd_kernel(const float* dy, const float* x, float* dk, int32_t N,
 
 /* ------------------------------------------------------------------------------------------- losses */
 /* Exact Euclidean distance transform + normalised signed distance map of compute_sdf1_1
- * (boundary_loss.py:40-67): mask fp32 [N][H][W] in {0,1} -> sdf.  scratch: 3*N*H*W + 2*N floats. */
+ * (boundary_loss.py:40-67): mask fp32 [N][H][W] -> sdf.  Foreground = the mask value truncated to uint8 is non-zero
+ * (the reference's astype(np.uint8); values in [0, 256); 0.5 and 0.99 are background).  A sample without foreground gets
+ * 0 everywhere, one of nothing but foreground -1 everywhere (the reference divides 0 / 0 there).  The distances are the
+ * correctly rounded roots of the exact squared distances while H*H + W*W < 2^24, within one more ulp beyond.
+ * scratch: 3*N*H*W + 2*N floats.  W <= 8192. */
 int csbsr_sdf(const float* mask, float* sdf, float* scratch, int32_t N, int32_t H, int32_t W, csbsr_stream_t s);
 /* Crack-oriented SR-loss weight of CrackOrientedExpWeight (oriented_weight.py:46-58,92-119): mask fp32 [N][H][W] ->
  * w_hr[N][H][W] = lambda * expf(-amp * d), d = exact Euclidean distance to the nearest foreground pixel (0 on

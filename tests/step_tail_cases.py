@@ -804,7 +804,7 @@ ELSEWHERE = {
     "csbsr_l1_fwd_bwd": "test_metrics_exact_gpu.py",
     "csbsr_segloss_reduce": "test_metrics_exact_gpu.py",
     "csbsr_segloss_finish": "test_metrics_exact_gpu.py",
-    "csbsr_sdf": "test_elementwise_gpu.py",
+    "csbsr_sdf": "test_edt_exact_gpu.py",
     "csbsr_crack_weight": "test_crack_weight_gpu.py",
 }
 NOT_COVERED = {}          # name -> the written reason (six words at least) why it has neither a row nor another suite
