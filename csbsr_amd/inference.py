@@ -8,7 +8,7 @@ returns the reference's final report, with the saved images and masks leaving th
 ``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
 of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device; on request (``measure_threshold``) with the
 crack's area, centerline length and mean width per image, and (``min_crack_px``) with the small blobs dropped and the same numbers per
-connected crack (csrc/components.hip)."""
+connected crack (csrc/components.hip), and (``width_radius``) with the local width at every centerline pixel (csrc/width.hip)."""
 import csv
 import os
 
@@ -21,6 +21,8 @@ from .engine import _ptr
 from .utils.estimate_metrics import psnr_ssim, iou_sweep, surface_distance_sweep, pr_sweep, pr_tol2
 from .utils.estimate_metrics import skeletonize, centerline_counts, cldice_scores, summarize_cldice, unit_threshold
 from .utils.estimate_metrics import label_components, component_min_px, _component_sums, _keep_from_sums, _table_from_sums
+from .utils.estimate_metrics import skeleton_width, summarize_width_hist, width_from_d2, _component_width, _width_columns
+from .utils.estimate_metrics import width_radius as _width_radius
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -293,6 +295,69 @@ def read_crack_instances(path):
     return out
 
 
+WIDTH_COLUMNS = ["name", "centerline_px", "saturated_px", "centerline_width_px", "median_width_px", "p95_width_px", "max_width_px", "y_widest",
+                 "x_widest"]
+INSTANCE_WIDTH_COLUMNS = ["name", "crack", "max_width_px", "y_widest", "x_widest"]
+
+
+def _yx(widest):
+    return ["", ""] if widest is None else [int(widest[0]), int(widest[1])]
+
+
+def _widest(y, x):
+    return None if y == "" else (int(y), int(x))
+
+
+def write_crack_widths(path, rows):
+    """crack_widths.csv: one row per image -- ``rows`` = (name, dict with WIDTH_COLUMNS' figures and ``widest`` = (y, x) or None); an empty
+    skeleton leaves y_widest and x_widest empty"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(WIDTH_COLUMNS)
+        for name, d in rows:
+            w.writerow([name, int(d["centerline_px"]), int(d["saturated_px"])] + [repr(float(d[k])) for k in WIDTH_COLUMNS[3:7]] + _yx(d["widest"]))
+
+
+def read_crack_widths(path):
+    """what ``write_crack_widths`` wrote: (name, dict) per image, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != WIDTH_COLUMNS:
+        raise ValueError(f"{path}: not a crack_widths.csv header: {rows[0]}")
+    out = []
+    for name, n, sat, mean, med, p95, mx, y, x in rows[1:]:
+        out.append((name, dict(centerline_px=int(n), saturated_px=int(sat), centerline_width_px=float(mean), median_width_px=float(med),
+                               p95_width_px=float(p95), max_width_px=float(mx), widest=_widest(y, x))))
+    return out
+
+
+def write_crack_instance_widths(path, rows):
+    """crack_instance_widths.csv: one row per kept crack -- ``rows`` = (name, the image's ``cracks`` list with max_width_px and widest) per
+    image; ``crack`` is the numbering of crack_instances.csv"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(INSTANCE_WIDTH_COLUMNS)
+        for name, cracks in rows:
+            for j, c in enumerate(cracks):
+                w.writerow([name, j, repr(float(c["max_width_px"]))] + _yx(c["widest"]))
+
+
+def read_crack_instance_widths(path):
+    """what ``write_crack_instance_widths`` wrote: (name, [dict(max_width_px, widest)]) per image, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != INSTANCE_WIDTH_COLUMNS:
+        raise ValueError(f"{path}: not a crack_instance_widths.csv header: {rows[0]}")
+    out = []
+    for name, j, mx, y, x in rows[1:]:
+        if not out or out[-1][0] != name:
+            out.append((name, []))
+        if int(j) != len(out[-1][1]):
+            raise ValueError(f"{path}: crack {j} of {name} is out of order")
+        out[-1][1].append(dict(max_width_px=float(mx), widest=_widest(y, x)))
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -457,8 +522,17 @@ def evaluate_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, surface_
 
 
 # ------------------------------------------------------------------------------------------------ prediction without ground truth
+def _hist_and_widest(d2, hist):
+    """one image's histogram with one more int64 behind it: max over the pixels of  d2 * H W + (H W - 1 - index) , whose maximum is the first
+    pixel in raster order with the largest d2 (< H W when d2 is 0 everywhere) -- a single integer reduction, nothing read by the host"""
+    hw = d2.numel()
+    key = d2.view(-1).to(torch.int64) * hw + torch.arange(hw - 1, -1, -1, dtype=torch.int64, device=d2.device)
+    return torch.cat([hist.view(-1).to(torch.int64), key.max().view(1)])
+
+
 @torch.no_grad()
-def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None):
+def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
+                    width_radius=None):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -487,17 +561,33 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     dict(y, x, area_px, length_px, mean_width_px, bbox=(y0, x0, y1, x1)) -- (y, x) the first pixel, length_px the crack's skeleton pixels, the
     box inclusive (``crack_instances``).  The integers of a unit still come back in one read, the unit's tables in one more.  With
     ``save_dir``, skeletons/<name> shows the kept skeleton, crack_stats.csv holds the values over K, and crack_instances.csv
-    (``write_crack_instances``) is written when the generator is exhausted.  None (the default) adds nothing."""
+    (``write_crack_instances``) is written when the generator is exhausted.  None (the default) adds nothing.
+
+    ``width_radius`` = r, a whole number 1 .. 128 (it needs ``measure_threshold`` too; anything else is a ValueError before the model runs),
+    takes the local width (``skeleton_width``) at the pixels of the skeleton the call reports -- with ``min_crack_px`` the kept
+    skeleton -- always against the region R of the whole stitched map: for a pixel of a kept component the nearest pixel outside K is never
+    closer than the nearest background pixel, so the distances against R are the distances against K.  New keys: max_width_px,
+    median_width_px, p95_width_px, centerline_width_px (floats, ``summarize_width_hist``; lower bounds where saturated_px > 0), saturated_px
+    (int), widest = (y, x) of the first centerline pixel in raster order with the largest d2 (None for an empty skeleton), width_hist (NumPy
+    int64 [r^2 + 2]) and width_d2 (device int32 [H, W]).  mean_width_px keeps its meaning, area over length.  With ``min_crack_px`` every dict
+    of ``cracks`` gains max_width_px and widest.  One more read per unit (the stacked histograms); the per-crack columns travel with the
+    unit's tables.  With ``save_dir``, crack_widths.csv (``write_crack_widths``) and, with ``min_crack_px``, crack_instance_widths.csv
+    (``write_crack_instance_widths``) are written when the generator is exhausted.  None (the default) adds nothing."""
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
     min_px = None
     if min_crack_px is not None:
         if measure is None:
             raise ValueError("min_crack_px filters what measure_threshold measures: give measure_threshold too")
         min_px = component_min_px(min_crack_px, "min_crack_px")
+    radius = None
+    if width_radius is not None:
+        if measure is None:
+            raise ValueError("width_radius measures the skeleton of measure_threshold: give measure_threshold too")
+        radius = _width_radius(width_radius, "width_radius")
     saver = None
     if save_dir is not None:
         saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
-    stats, instances = [], []
+    stats, instances, widths = [], [], []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -520,7 +610,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         kernels = torch.cat(kernels)
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
-        extra, px, kept_labels, tables = [], None, [], None
+        extra, px, kept_labels, tables, wd2, whist = [], None, [], None, [], []
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
@@ -531,6 +621,10 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 if min_px is None:
                     skel_u8[o:o + H * W] = sk * 255
                     px.append(torch.stack([(map_f32[o:o + H * W] - t32 > 0).sum(), sk.sum()]))
+                    if radius is not None:
+                        d2, hist = skeleton_width(plane, sk.view(1, H, W), measure, radius)
+                        wd2.append(d2.view(H, W))
+                        whist.append(_hist_and_widest(d2, hist))
                     continue
                 labels = label_components(plane, measure)
                 acc = _component_sums(labels, sk)
@@ -538,12 +632,18 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 sk = sk * keep.view(-1)                      # skeleton(R) & K = skeleton(K)
                 skel_u8[o:o + H * W] = sk * 255
                 table = _table_from_sums(labels, acc, min_px)
+                if radius is not None:                       # against R: for a kept pixel the distance against K is the same
+                    d2, hist = skeleton_width(plane, sk.view(1, H, W), measure, radius)
+                    wd2.append(d2.view(H, W))
+                    whist.append(_hist_and_widest(d2, hist))
+                    table = torch.cat([table, _width_columns(table, _component_width(labels, d2), W)], 1)
                 table[:, 0] = j                              # the image within the unit
                 tables.append(table)
                 kept_labels.append(kept.view(H, W))
                 px.append(torch.stack([keep.sum(), sk.sum(), (labels != 0).sum()]))
             px = torch.stack(px).cpu().tolist()              # the unit's integers in one read
             tables = torch.cat(tables).cpu().numpy() if min_px is not None else None         # and the unit's tables in one more
+            whist = torch.stack(whist).cpu().numpy() if radius is not None else None         # the unit's histograms (and widest keys) in one
             extra = [skel_u8]
         if saver is not None:
             planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
@@ -557,9 +657,20 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 item.update(crack_px=crack, skeleton_px=skel, mean_width_px=mean_width(crack, skel))
                 stats.append((loader.names[i], crack, skel, item["mean_width_px"]))
                 if min_px is not None:
-                    cracks = crack_instances(tables[tables[:, 0] == j].tolist(), W)
+                    rows = tables[tables[:, 0] == j]
+                    cracks = crack_instances(rows[:, :8].tolist(), W)
+                    if radius is not None:
+                        for c, (m, y, x) in zip(cracks, rows[:, 8:].tolist()):
+                            c.update(max_width_px=width_from_d2(m), widest=(y, x) if m > 0 else None)
                     item.update(removed_px=int(px[j][2]) - crack, n_cracks=len(cracks), labels=kept_labels[j], cracks=cracks)
                     instances.append((loader.names[i], cracks))
+                if radius is not None:
+                    hist, key = whist[j, :-1], int(whist[j, -1])
+                    w = summarize_width_hist(hist, radius)
+                    w["widest"] = divmod(H * W - 1 - key % (H * W), W) if key >= H * W else None        # key = max d2 * H W + (H W - 1 - index)
+                    item.update({k: w[k] for k in ("max_width_px", "median_width_px", "p95_width_px", "centerline_width_px", "saturated_px",
+                                                   "widest")}, width_hist=hist.copy(), width_d2=wd2[j])
+                    widths.append((loader.names[i], w))
             yield item
     if saver is not None:
         saver.drain()
@@ -567,3 +678,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             write_crack_stats(os.path.join(save_dir, "crack_stats.csv"), stats)
         if min_px is not None:
             write_crack_instances(os.path.join(save_dir, "crack_instances.csv"), instances)
+        if radius is not None:
+            write_crack_widths(os.path.join(save_dir, "crack_widths.csv"), widths)
+            if min_px is not None:
+                write_crack_instance_widths(os.path.join(save_dir, "crack_instance_widths.csv"), instances)

@@ -299,6 +299,126 @@ def keep_components(labels, min_px):
     return _keep_from_sums(labels, _component_sums(labels), k)[0]
 
 
+# ------------------------------------------------------------------------------------------- local crack width
+WIDTH_MAX_RADIUS = 128                                       # csrc/width.hip: csbsr_width_max_radius()
+WIDTH_TABLE_COLUMNS = ("plane", "label", "max_d2", "y", "x")
+
+
+def width_radius(max_radius, what="max_radius"):
+    """the search radius of the local width, in pixels: a whole number 1 .. 128 (Python or NumPy, not a bool), anything else is a ValueError"""
+    if (isinstance(max_radius, (bool, np.bool_)) or not isinstance(max_radius, (int, np.integer))
+            or not 1 <= max_radius <= WIDTH_MAX_RADIUS):
+        raise ValueError(f"{what} is a whole number 1 .. {WIDTH_MAX_RADIUS}, got {max_radius!r}")
+    return int(max_radius)
+
+
+def skeleton_width(planes, skeleton, threshold=0.5, max_radius=64):
+    """The squared distance from every skeleton pixel to the nearest background pixel of its plane (csrc/width.hip): (d2, hist), int32 device
+    tensors [N, H, W] and [N, r^2 + 2] for fp32 planes [..., H, W] and a uint8 skeleton of the same shape (``skeletonize``'s, or any subset
+    of it).  The region is ``planes - threshold > 0`` in fp32 (NaN -> not set), the background the other pixels of the SAME plane: the image
+    border, the next plane and the padding of a packed row are no background.  d2 = min(r^2 + 1, the exact squared distance) at a skeleton
+    pixel -- r^2 + 1 means wider than the search radius r = ``max_radius``: saturated --, 0 elsewhere and at a skeleton pixel outside the
+    region.  hist[n][v] counts the skeleton pixels of plane n with d2 == v.  The local width is ``width_from_d2``."""
+    t, r = skeleton_threshold(threshold), width_radius(max_radius)
+    L.load()
+    x = _dev32(planes)
+    if not (torch.is_tensor(skeleton) and skeleton.dtype == torch.uint8):
+        raise ValueError("skeleton is a uint8 tensor of the planes' shape")
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    x = x.reshape(-1, H, W)
+    if skeleton.dim() < 2 or tuple(skeleton.shape[-2:]) != (H, W) or skeleton.numel() != x.numel():      # [N, H, W] or the planes' own shape
+        raise ValueError(f"the skeleton is {tuple(skeleton.shape)}, the planes are {tuple(planes.shape)}")
+    N, dev = x.shape[0], x.device
+    sk = skeleton.to(dev).contiguous()
+    d2 = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+    hist = torch.empty(N, r * r + 2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("csbsr_skeleton_width", _ptr(x), t, _ptr(sk), N, H, W, r, _ptr(d2), _ptr(hist), L.stream(dev))
+    return d2, hist
+
+
+def _component_width(labels, d2):
+    """the accumulators of csbsr_component_width, int32 [N, 2, H * W]: only the slots of root pixels hold values"""
+    N, H, W = labels.shape
+    if not (torch.is_tensor(d2) and d2.dtype == torch.int32 and tuple(d2.shape) == (N, H, W)):
+        raise ValueError("d2 is the int32 tensor [N, H, W] of skeleton_width, one value per label")
+    d2 = d2.to(labels.device).contiguous()
+    wacc = torch.empty(N, 2, H * W, dtype=torch.int32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        L.call("csbsr_component_width", _ptr(labels), _ptr(d2), N, H, W, _ptr(wacc), L.stream(labels.device))
+    return wacc
+
+
+def _width_columns(table, wacc, W):
+    """(max_d2, y, x) int32 [M, 3] for the rows of a component table (plane, label, ...): y = x = -1 where max_d2 is 0"""
+    n, i = table[:, 0].long(), table[:, 1].long() - 1
+    m, at = wacc[n, 0, i], wacc[n, 1, i]
+    y = torch.where(at >= 0, torch.div(at, W, rounding_mode="floor"), at)
+    return torch.stack([m, y, torch.where(at >= 0, at - y * W, at)], 1).to(torch.int32)
+
+
+def component_width_table(labels, d2, min_px=1):
+    """The widest point of every component: int32 device tensor [M, 5] = (plane, label, max_d2, y, x) with exactly the rows of
+    ``component_table(labels, None, min_px)``, in that order.  max_d2 is the largest ``d2`` (``skeleton_width``'s) over the component's pixels,
+    (y, x) the first pixel in raster order that attains it; a component without a pixel of d2 > 0 has (0, -1, -1)."""
+    rows = component_table(labels, None, min_px)
+    labels = _labels(labels)
+    return torch.cat([rows[:, :2], _width_columns(rows, _component_width(labels, d2), labels.shape[2])], 1)
+
+
+def _host_ints(a):
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a)
+
+
+def width_from_d2(d2):
+    """the local width in pixels, fp64 on the host: 2 sqrt(d2) - 1, and 0.0 where d2 = 0 (ints, NumPy arrays or tensors; a Python float for a
+    scalar).  A straight bar of odd width w gives exactly w on its centerline; an even width w gives w - 1, because the centerline lies on one
+    of the two middle rows -- this one-pixel bias is left as it is."""
+    d = _host_ints(d2).astype(np.float64)
+    w = np.where(d > 0, 2.0 * np.sqrt(d) - 1.0, 0.0)
+    return float(w) if w.ndim == 0 else w
+
+
+def _hist_row(hist_row):
+    h = _host_ints(hist_row).astype(np.int64)
+    if h.ndim != 1 or h.size < 3:
+        raise ValueError(f"a width histogram is one plane's row of r^2 + 2 counts, got shape {h.shape}")
+    return h
+
+
+def summarize_width_hist(hist_row, max_radius):
+    """The width figures of one plane from its histogram (``skeleton_width``'s hist[n]), fp64 on the host: centerline_px (the bins >= 1),
+    outside_px (bin 0), saturated_px (the last bin), and over the centerline pixels' local widths (``width_from_d2``) centerline_width_px
+    (their mean), median_width_px (the element of zero-based rank (n - 1) // 2 of the sorted d2), p95_width_px (rank ceil(0.95 n) - 1) and
+    max_width_px.  Saturated pixels take part with r^2 + 1: with saturated_px > 0 the figures are lower bounds.  n = 0: every width 0.0."""
+    r = width_radius(max_radius)
+    h = _hist_row(hist_row)
+    if h.size != r * r + 2:
+        raise ValueError(f"the histogram of radius {r} has {r * r + 2} bins, got {h.size}")
+    c = h[1:]
+    n = int(c.sum())
+    out = {"centerline_px": n, "outside_px": int(h[0]), "saturated_px": int(h[-1])}
+    if n == 0:
+        out.update(centerline_width_px=0.0, median_width_px=0.0, p95_width_px=0.0, max_width_px=0.0)
+        return out
+    w = width_from_d2(np.arange(1, h.size))
+    cum = np.cumsum(c)
+    at = lambda rank: float(w[int(np.searchsorted(cum, rank + 1))])                 # the first bin whose cumulative count exceeds the rank
+    out.update(centerline_width_px=float(np.dot(c.astype(np.float64), w) / n), median_width_px=at((n - 1) // 2),
+               p95_width_px=at(-(-95 * n // 100) - 1), max_width_px=float(w[int(np.nonzero(c)[0][-1])]))
+    return out
+
+
+def centerline_px_at_least(hist_row, width_px):
+    """the centerline pixels whose local width is >= ``width_px``, from one plane's histogram: the length of crack wider than a limit
+    (saturated pixels count with the width of r^2 + 1; bin 0 never counts)"""
+    h = _hist_row(hist_row)
+    w = width_from_d2(np.arange(1, h.size))
+    return int(h[1:][w >= float(width_px)].sum())
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

@@ -689,6 +689,29 @@ int csbsr_component_sums(const int32_t* labels, const uint8_t* skeleton, int32_t
 int csbsr_component_keep(const int32_t* labels, const int32_t* acc, int32_t N, int32_t H, int32_t W, int32_t min_px, uint8_t* keep,
                          int32_t* labels_out, csbsr_stream_t s);
 
+/* Local crack width: the exact squared distance from every centerline pixel to the plane's nearest background pixel, its histogram and the
+ * widest point of every component (csrc/width.hip).  Region R: x - threshold > 0 in fp32 (NaN -> not in R; the threshold is
+ * finite), the predicate of csbsr_skeleton_init and csbsr_ccl_label.  Background: the pixels of the SAME plane outside R -- nothing outside
+ * the plane, no other plane of the batch, no padding bit.  d2(p) = min(r^2 + 1, min over background q of |p - q|^2), r = max_radius;
+ * r^2 + 1 = saturated (wider than the search radius; the value everywhere in a plane without background).
+ *   csbsr_width_max_radius : the largest radius, 128.
+ *   csbsr_width_tile       : the pixels one workgroup owns, rows and columns.
+ *   csbsr_skeleton_width   : planes fp32 [N][H][W], skeleton uint8 [N][H][W].  d2 int32 [N][H][W], written at EVERY pixel (the caller does not
+ *                            zero it): 0 where skeleton == 0, d2 as above where skeleton != 0 (0 for a skeleton pixel outside R).  hist int32
+ *                            [N][r^2 + 2], zeroed by the entry on the stream: hist[n][v] = skeleton pixels of plane n with d2 == v; bin 0 the
+ *                            skeleton pixels outside R, bin r^2 + 1 the saturated ones.
+ *   csbsr_component_width  : labels int32 [N][H][W] of csbsr_ccl_label, d2 as above.  wacc int32 [N][2][H W], indexed by ROOT pixel i = label - 1:
+ *                            wacc[n][0][i] = the largest d2 over the component's pixels (0 if none is > 0), [1][i] = the linear index of the
+ *                            first pixel in raster order that attains it (-1 when [0][i] is 0).  ONLY the slots of root pixels are written.
+ * 1 <= H, W <= 8192, 1 <= N <= 65535, 1 <= max_radius <= 128; a null pointer, a size or radius outside these or a non-finite threshold is
+ * refused (non-zero return) before anything is launched.  Integer atomics only: results are run-to-run identical.  No entry synchronises
+ * with the host. */
+int32_t csbsr_width_max_radius(void);
+int csbsr_width_tile(int32_t* th, int32_t* tw);
+int csbsr_skeleton_width(const float* planes, float threshold, const uint8_t* skeleton, int32_t N, int32_t H, int32_t W, int32_t max_radius,
+                         int32_t* d2, int32_t* hist, csbsr_stream_t s);
+int csbsr_component_width(const int32_t* labels, const int32_t* d2, int32_t N, int32_t H, int32_t W, int32_t* wacc, csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
