@@ -8,7 +8,8 @@ returns the reference's final report, with the saved images and masks leaving th
 ``predict_dataset`` is the other driver of test.py, ``inference_tti_building`` (inference.py:210-273): unlabeled LR images of any size out
 of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device; on request (``measure_threshold``) with the
 crack's area, centerline length and mean width per image, and (``min_crack_px``) with the small blobs dropped and the same numbers per
-connected crack (csrc/components.hip), and (``width_radius``) with the local width at every centerline pixel (csrc/width.hip)."""
+connected crack (csrc/components.hip), (``width_radius``) with the local width at every centerline pixel (csrc/width.hip), and
+(``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip)."""
 import csv
 import os
 
@@ -23,6 +24,8 @@ from .utils.estimate_metrics import skeletonize, centerline_counts, cldice_score
 from .utils.estimate_metrics import label_components, component_min_px, _component_sums, _keep_from_sums, _table_from_sums
 from .utils.estimate_metrics import skeleton_width, summarize_width_hist, width_from_d2, _component_width, _width_columns
 from .utils.estimate_metrics import width_radius as _width_radius
+from .utils.estimate_metrics import skeleton_topology, summarize_topology, geodesic_length, orientation_shares, euler_number, mean_width_geodesic
+from .utils.estimate_metrics import _junction_labels, _count_roots, _component_topology, _topology_columns, TOPO_COUNTS, TOPO_ACC
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -358,6 +361,75 @@ def read_crack_instance_widths(path):
     return out
 
 
+TOPOLOGY_CSV_COLUMNS = ["name", "endpoints", "junctions", "junction_px", "isolated_px", "loops", "h", "v", "d_se", "d_sw", "length_geodesic_px",
+                        "share_h", "share_v", "share_se", "share_sw", "mean_width_geodesic_px"]
+INSTANCE_TOPOLOGY_COLUMNS = ["name", "crack", "endpoints", "junctions", "loops", "h", "v", "d_se", "d_sw", "length_geodesic_px", "share_h",
+                             "share_v", "share_se", "share_sw"]
+
+
+def crack_topology(sums, length_px):
+    """the topology keys of one crack from its nine sums of ``component_topology_table`` (end, junction_px, h, v, d_se, d_sw, q4, isolated,
+    junctions) and its centerline pixels: the centerline of one crack is one component, so loops = 1 - chi (0 - chi = 0 without a centerline)"""
+    end, _, h, v, dse, dsw, q4, _, junctions = (int(k) for k in sums)
+    links = (h, v, dse, dsw)
+    return dict(endpoints=end, junctions=junctions, loops=(1 if length_px else 0) - euler_number(length_px, links, q4), links=links,
+                length_geodesic_px=geodesic_length(*links), orientation=orientation_shares(*links))
+
+
+def write_crack_topology(path, rows):
+    """crack_topology.csv: one row per image -- ``rows`` = (name, dict with the topology keys of ``predict_dataset``)"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(TOPOLOGY_CSV_COLUMNS)
+        for name, d in rows:
+            w.writerow([name] + [int(d[k]) for k in TOPOLOGY_CSV_COLUMNS[1:6]] + [int(k) for k in d["links"]] + [repr(float(d["length_geodesic_px"]))]
+                       + [repr(float(k)) for k in d["orientation"]] + [repr(float(d["mean_width_geodesic_px"]))])
+
+
+def read_crack_topology(path):
+    """what ``write_crack_topology`` wrote: (name, dict) per image, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != TOPOLOGY_CSV_COLUMNS:
+        raise ValueError(f"{path}: not a crack_topology.csv header: {rows[0]}")
+    out = []
+    for r in rows[1:]:
+        d = {k: int(v) for k, v in zip(TOPOLOGY_CSV_COLUMNS[1:6], r[1:6])}
+        d.update(links=tuple(int(v) for v in r[6:10]), length_geodesic_px=float(r[10]), orientation=tuple(float(v) for v in r[11:15]),
+                 mean_width_geodesic_px=float(r[15]))
+        out.append((r[0], d))
+    return out
+
+
+def write_crack_instance_topology(path, rows):
+    """crack_instance_topology.csv: one row per kept crack -- ``rows`` = (name, the image's ``cracks`` list with the topology keys) per image;
+    ``crack`` is the numbering of crack_instances.csv"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(INSTANCE_TOPOLOGY_COLUMNS)
+        for name, cracks in rows:
+            for j, c in enumerate(cracks):
+                w.writerow([name, j, int(c["endpoints"]), int(c["junctions"]), int(c["loops"])] + [int(k) for k in c["links"]]
+                           + [repr(float(c["length_geodesic_px"]))] + [repr(float(k)) for k in c["orientation"]])
+
+
+def read_crack_instance_topology(path):
+    """what ``write_crack_instance_topology`` wrote: (name, [dict]) per image, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != INSTANCE_TOPOLOGY_COLUMNS:
+        raise ValueError(f"{path}: not a crack_instance_topology.csv header: {rows[0]}")
+    out = []
+    for r in rows[1:]:
+        if not out or out[-1][0] != r[0]:
+            out.append((r[0], []))
+        if int(r[1]) != len(out[-1][1]):
+            raise ValueError(f"{path}: crack {r[1]} of {r[0]} is out of order")
+        out[-1][1].append(dict(endpoints=int(r[2]), junctions=int(r[3]), loops=int(r[4]), links=tuple(int(v) for v in r[5:9]),
+                               length_geodesic_px=float(r[9]), orientation=tuple(float(v) for v in r[10:14])))
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -530,9 +602,18 @@ def _hist_and_widest(d2, hist):
     return torch.cat([hist.view(-1).to(torch.int64), key.max().view(1)])
 
 
+def _topology_ints(sk):
+    """(topo, the image's twelve integers as one int64 device tensor -- the ten counts, the skeleton's 8-connected components and the
+    junction clusters --, the junction labels) of one skeleton plane [1, H, W]: nothing is read by the host"""
+    topo, counts = skeleton_topology(sk)
+    jl = _junction_labels(topo)
+    ints = torch.cat([counts.view(-1).to(torch.int64), _count_roots(label_components(sk.to(torch.float32), 0.5)), _count_roots(jl)])
+    return topo, ints, jl
+
+
 @torch.no_grad()
 def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
-                    width_radius=None):
+                    width_radius=None, topology=False):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -572,7 +653,23 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     int64 [r^2 + 2]) and width_d2 (device int32 [H, W]).  mean_width_px keeps its meaning, area over length.  With ``min_crack_px`` every dict
     of ``cracks`` gains max_width_px and widest.  One more read per unit (the stacked histograms); the per-crack columns travel with the
     unit's tables.  With ``save_dir``, crack_widths.csv (``write_crack_widths``) and, with ``min_crack_px``, crack_instance_widths.csv
-    (``write_crack_instance_widths``) are written when the generator is exhausted.  None (the default) adds nothing."""
+    (``write_crack_instance_widths``) are written when the generator is exhausted.  None (the default) adds nothing.
+
+    ``topology`` = True (only True and False are accepted, and True needs ``measure_threshold``; anything else is a ValueError before the
+    model runs) describes the shape of the skeleton the call reports -- with ``min_crack_px`` the kept skeleton -- (DESIGN 1.13,
+    ``skeleton_topology``).  New keys: endpoints, junction_px, isolated_px (pixels of that class), junctions (the 8-connected clusters of
+    junction pixels), loops (the enclosed cells: the skeleton's 8-connected components minus its Euler number), links = (h, v, d_se, d_sw),
+    length_geodesic_px (``geodesic_length``: reads long by up to 8.24 % on a straight line that is neither axis-parallel nor at 45 degrees),
+    orientation (``orientation_shares``), mean_width_geodesic_px = crack_px / length_geodesic_px (0.0 for a length of 0) and topology_map
+    (device uint8 [H, W], the topo bytes).  skeleton_px, length_px and mean_width_px keep their meaning.  With ``min_crack_px`` every dict of
+    ``cracks`` gains endpoints, junctions, loops, links, length_geodesic_px and orientation (``crack_topology``).  The integers travel in the
+    unit's one read, the per-crack columns with the unit's tables.  With ``save_dir``, crack_topology.csv (``write_crack_topology``) and,
+    with ``min_crack_px``, crack_instance_topology.csv (``write_crack_instance_topology``) are written when the generator is exhausted.
+    False (the default) adds nothing: no key, no file, no launch."""
+    if topology is not True and topology is not False:
+        raise ValueError(f"topology is True or False, got {topology!r}")
+    if topology and measure_threshold is None:
+        raise ValueError("topology describes the skeleton of measure_threshold: give measure_threshold too")
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
     min_px = None
     if min_crack_px is not None:
@@ -587,7 +684,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     saver = None
     if save_dir is not None:
         saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
-    stats, instances, widths = [], [], []
+    stats, instances, widths, topologies = [], [], [], []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -610,7 +707,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         kernels = torch.cat(kernels)
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
-        extra, px, kept_labels, tables, wd2, whist = [], None, [], None, [], []
+        extra, px, kept_labels, tables, wd2, whist, tmaps = [], None, [], None, [], [], []
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
@@ -621,6 +718,10 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 if min_px is None:
                     skel_u8[o:o + H * W] = sk * 255
                     px.append(torch.stack([(map_f32[o:o + H * W] - t32 > 0).sum(), sk.sum()]))
+                    if topology:
+                        topo, tints, _ = _topology_ints(sk.view(1, H, W))
+                        tmaps.append(topo.view(H, W))
+                        px[-1] = torch.cat([px[-1], tints])
                     if radius is not None:
                         d2, hist = skeleton_width(plane, sk.view(1, H, W), measure, radius)
                         wd2.append(d2.view(H, W))
@@ -637,10 +738,15 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     wd2.append(d2.view(H, W))
                     whist.append(_hist_and_widest(d2, hist))
                     table = torch.cat([table, _width_columns(table, _component_width(labels, d2), W)], 1)
+                px.append(torch.stack([keep.sum(), sk.sum(), (labels != 0).sum()]))
+                if topology:                                 # of the kept skeleton; a removed component has no pixel in it
+                    topo, tints, jl = _topology_ints(sk.view(1, H, W))
+                    tmaps.append(topo.view(H, W))
+                    px[-1] = torch.cat([px[-1], tints])
+                    table = torch.cat([table, _topology_columns(table, _component_topology(labels, topo, jl))], 1)
                 table[:, 0] = j                              # the image within the unit
                 tables.append(table)
                 kept_labels.append(kept.view(H, W))
-                px.append(torch.stack([keep.sum(), sk.sum(), (labels != 0).sum()]))
             px = torch.stack(px).cpu().tolist()              # the unit's integers in one read
             tables = torch.cat(tables).cpu().numpy() if min_px is not None else None         # and the unit's tables in one more
             whist = torch.stack(whist).cpu().numpy() if radius is not None else None         # the unit's histograms (and widest keys) in one
@@ -660,8 +766,11 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     rows = tables[tables[:, 0] == j]
                     cracks = crack_instances(rows[:, :8].tolist(), W)
                     if radius is not None:
-                        for c, (m, y, x) in zip(cracks, rows[:, 8:].tolist()):
+                        for c, (m, y, x) in zip(cracks, rows[:, 8:11].tolist()):
                             c.update(max_width_px=width_from_d2(m), widest=(y, x) if m > 0 else None)
+                    if topology:
+                        for c, sums in zip(cracks, rows[:, -TOPO_ACC:].tolist()):
+                            c.update(crack_topology(sums, c["length_px"]))
                     item.update(removed_px=int(px[j][2]) - crack, n_cracks=len(cracks), labels=kept_labels[j], cracks=cracks)
                     instances.append((loader.names[i], cracks))
                 if radius is not None:
@@ -671,6 +780,13 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     item.update({k: w[k] for k in ("max_width_px", "median_width_px", "p95_width_px", "centerline_width_px", "saturated_px",
                                                    "widest")}, width_hist=hist.copy(), width_d2=wd2[j])
                     widths.append((loader.names[i], w))
+                if topology:
+                    tp = summarize_topology(px[j][-TOPO_COUNTS - 2:-2], px[j][-2], px[j][-1])
+                    tp = {k: tp[k] for k in ("endpoints", "junctions", "junction_px", "isolated_px", "loops", "links", "length_geodesic_px",
+                                             "orientation")}
+                    tp["mean_width_geodesic_px"] = mean_width_geodesic(crack, tp["length_geodesic_px"])
+                    item.update(tp, topology_map=tmaps[j])
+                    topologies.append((loader.names[i], tp))
             yield item
     if saver is not None:
         saver.drain()
@@ -682,3 +798,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             write_crack_widths(os.path.join(save_dir, "crack_widths.csv"), widths)
             if min_px is not None:
                 write_crack_instance_widths(os.path.join(save_dir, "crack_instance_widths.csv"), instances)
+        if topology:
+            write_crack_topology(os.path.join(save_dir, "crack_topology.csv"), topologies)
+            if min_px is not None:
+                write_crack_instance_topology(os.path.join(save_dir, "crack_instance_topology.csv"), instances)

@@ -419,6 +419,120 @@ def centerline_px_at_least(hist_row, width_px):
     return int(h[1:][w >= float(width_px)].sum())
 
 
+# ------------------------------------------------------------------------------------------- crack topology
+TOPO_COUNTS = 10                                             # csrc/topology.hip: the counters per plane
+TOPO_ACC = 9                                                 # and the accumulators per root pixel
+TOPOLOGY_COLUMNS = ("V", "isolated", "end", "path", "junction_px", "h", "v", "d_se", "d_sw", "q4")
+TOPOLOGY_TABLE_COLUMNS = ("plane", "label", "end", "junction_px", "h", "v", "d_se", "d_sw", "q4", "isolated", "junctions")
+TOPO_ISOLATED, TOPO_END, TOPO_PATH, TOPO_JUNCTION = 1, 2, 3, 4        # bits 0-2 of a topo byte
+TOPO_QUAD, TOPO_E, TOPO_S, TOPO_SE, TOPO_SW = 8, 16, 32, 64, 128      # and its flags
+
+
+def skeleton_topology(skeleton):
+    """Node class, owned links and full quads of every pixel of binary planes (csrc/topology.hip): (topo, counts), device tensors
+    uint8 [N, H, W] and int32 [N, 10], for a uint8 tensor [..., H, W] that is set where it is non-zero (``skeletonize``'s, or any other).
+    topo: bits 0-2 the class -- 0 clear, 1 isolated, 2 end, 3 path, 4 junction --, bit 3 the pixel owns a full quad, bits 4 .. 7 it owns an
+    E, S, SE, SW link.  counts: ``TOPOLOGY_COLUMNS`` per plane.  Planes are independent and nothing outside a plane is set."""
+    if not (torch.is_tensor(skeleton) and skeleton.dtype == torch.uint8 and skeleton.dim() >= 2):
+        raise ValueError("skeleton is a uint8 tensor [..., H, W]")
+    L.load()
+    dev = skeleton.device if skeleton.is_cuda else torch.device("cuda:0")
+    H, W = int(skeleton.shape[-2]), int(skeleton.shape[-1])
+    sk = skeleton.to(dev).reshape(-1, H, W).contiguous()
+    N = sk.shape[0]
+    topo = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+    counts = torch.empty(N, TOPO_COUNTS, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("csbsr_skeleton_topology", _ptr(sk), N, H, W, _ptr(topo), _ptr(counts), L.stream(dev))
+    return topo, counts
+
+
+def _junction_labels(topo):
+    """the 8-connected clusters of the junction pixels of ``skeleton_topology``'s topo, labelled by ``label_components``"""
+    return label_components(((topo & 7) == TOPO_JUNCTION).to(torch.float32), 0.5)
+
+
+def _count_roots(labels):
+    """the components per plane, int64 [N]: the pixels that carry their own linear index + 1"""
+    N, H, W = labels.shape
+    return (labels.view(N, H * W) == torch.arange(1, H * W + 1, dtype=torch.int32, device=labels.device)).sum(1)
+
+
+def _component_topology(labels, topo, jlabels=None):
+    """the accumulators of csbsr_component_topology, int32 [N, 9, H * W]: only the slots of root pixels hold values"""
+    N, H, W = labels.shape
+    if not (torch.is_tensor(topo) and topo.dtype == torch.uint8 and tuple(topo.shape) == (N, H, W)):
+        raise ValueError("topo is the uint8 tensor [N, H, W] of skeleton_topology, one value per label")
+    topo = topo.to(labels.device).contiguous()
+    tacc = torch.empty(N, TOPO_ACC, H * W, dtype=torch.int32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        L.call("csbsr_component_topology", _ptr(labels), _ptr(topo), None if jlabels is None else _ptr(jlabels), N, H, W, _ptr(tacc),
+               L.stream(labels.device))
+    return tacc
+
+
+def _topology_columns(table, tacc):
+    """the nine sums, int32 [M, 9], for the rows of a component table (plane, label, ...)"""
+    return tacc[table[:, 0].long(), :, table[:, 1].long() - 1]
+
+
+def component_topology_table(labels, topo, min_px=1):
+    """The topology sums of every component: int32 device tensor [M, 11] = ``TOPOLOGY_TABLE_COLUMNS`` with exactly the rows of
+    ``component_table(labels, None, min_px)``, in that order.  The sums run over the component's pixels of ``topo`` (``skeleton_topology``'s);
+    junctions counts the 8-connected clusters of junction pixels by their first pixel in raster order."""
+    rows = component_table(labels, None, min_px)
+    labels = _labels(labels)
+    if not (torch.is_tensor(topo) and topo.dtype == torch.uint8 and tuple(topo.shape) == tuple(labels.shape)):
+        raise ValueError("topo is the uint8 tensor [N, H, W] of skeleton_topology, one value per label")
+    topo = topo.to(labels.device).contiguous()
+    return torch.cat([rows[:, :2], _topology_columns(rows, _component_topology(labels, topo, _junction_labels(topo)))], 1)
+
+
+_SQRT2 = float(np.sqrt(2.0))
+
+
+def geodesic_length(h, v, d_se, d_sw):
+    """the chain-code length between pixel centres, fp64 on the host: h + v + sqrt(2) (d_se + d_sw) (ints, NumPy arrays or tensors; a Python
+    float for scalars).  A straight run of n pixels gives n - 1, a 45-degree run sqrt(2) (n - 1); a straight line at another angle reads long
+    by up to 8.24 % (at 22.5 degrees) -- this bias is left as it is, like the even-width bias of ``width_from_d2``."""
+    h, v, a, b = (_host_ints(t).astype(np.float64) for t in (h, v, d_se, d_sw))
+    n = h + v + _SQRT2 * (a + b)
+    return float(n) if n.ndim == 0 else n
+
+
+def orientation_shares(h, v, d_se, d_sw):
+    """the shares of the geodesic length that run horizontally, vertically and along the two diagonals: a 4-tuple of Python floats that sums
+    to 1, all zeros for a length of 0"""
+    parts = (float(h), float(v), _SQRT2 * float(d_se), _SQRT2 * float(d_sw))
+    n = geodesic_length(h, v, d_se, d_sw)
+    return tuple(p / n for p in parts) if n > 0 else (0.0, 0.0, 0.0, 0.0)
+
+
+def euler_number(V, links, q4):
+    """chi = V - (h + v + d_se + d_sw) + q4 of the cell complex of set pixels, owned links and full quads: components minus enclosed cells"""
+    return int(V) - sum(int(k) for k in links) + int(q4)
+
+
+def mean_width_geodesic(crack_px, length):
+    """crack_px / length in fp64, 0.0 for a length of 0"""
+    return float(crack_px) / float(length) if length else 0.0
+
+
+def summarize_topology(counts_row, n_components, n_junctions):
+    """The topology figures of one plane from its row of ``skeleton_topology``'s counts, the number of 8-connected components of the plane and
+    the number of junction clusters: a dict of skeleton_px, endpoints, junctions, junction_px, isolated_px, path_px, links = (h, v, d_se,
+    d_sw), quads, euler, components, loops = components - euler (the enclosed cells), length_geodesic_px and orientation."""
+    c = _host_ints(counts_row).astype(np.int64)
+    if c.shape != (TOPO_COUNTS,):
+        raise ValueError(f"a row of topology counts has {TOPO_COUNTS} integers, got shape {c.shape}")
+    V, iso, end, path, jpx, h, v, dse, dsw, q4 = (int(k) for k in c)
+    links = (h, v, dse, dsw)
+    chi = euler_number(V, links, q4)
+    return {"skeleton_px": V, "endpoints": end, "junctions": int(n_junctions), "junction_px": jpx, "isolated_px": iso, "path_px": path,
+            "links": links, "quads": q4, "euler": chi, "components": int(n_components), "loops": int(n_components) - chi,
+            "length_geodesic_px": geodesic_length(*links), "orientation": orientation_shares(*links)}
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

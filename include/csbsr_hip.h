@@ -712,6 +712,27 @@ int csbsr_skeleton_width(const float* planes, float threshold, const uint8_t* sk
                          int32_t* d2, int32_t* hist, csbsr_stream_t s);
 int csbsr_component_width(const int32_t* labels, const int32_t* d2, int32_t N, int32_t H, int32_t W, int32_t* wacc, csbsr_stream_t s);
 
+/* Crack topology: node class, owned links and full quads of every pixel of a binary plane, their counts, and the same sums per component
+ * (csrc/topology.hip).  A pixel of ``skeleton`` is set where its byte is non-zero; everything outside the plane -- another
+ * plane of the batch too -- is clear.  With the 8 neighbours read in the ring order N, NE, E, SE, S, SW, W, NW (cyclically), n8 = the set
+ * neighbours and A = the positions where a clear neighbour is followed by a set one, the class of a set pixel is 1 isolated (n8 == 0),
+ * 2 end (A == 1), 4 junction (A >= 3), 3 path (the rest); a clear pixel has class 0.  A link belongs to its first pixel in raster order:
+ * E and S when both pixels are set, SE when both are set and neither the E nor the S neighbour is, SW when both are set and neither the W
+ * nor the S neighbour is.  A pixel owns a full quad when it and its E, S and SE neighbours are all set.
+ *   csbsr_skeleton_topology  : skeleton uint8 [N][H][W].  topo uint8 [N][H][W], written at EVERY pixel (another array than the skeleton):
+ *                              bits 0-2 the class, bit 3 the full quad, bits 4 .. 7 the E, S, SE, SW link; 0 at a clear pixel.  counts int32
+ *                              [N][10], zeroed by the entry on the stream: V (set pixels), isolated, end, path, junction_px, h (E links),
+ *                              v (S links), d_se, d_sw, q4 (full quads).
+ *   csbsr_component_topology : labels int32 [N][H][W] of csbsr_ccl_label, topo as above, jlabels int32 [N][H][W] = csbsr_ccl_label's labels of
+ *                              the junction pixels, or NULL.  tacc int32 [N][9][H W], indexed by ROOT pixel i = label - 1: the sums over the
+ *                              component's pixels of end, junction_px, h, v, d_se, d_sw, q4, isolated, and junctions = the pixels whose
+ *                              jlabels value is their own linear index + 1 (0 without jlabels).  ONLY the slots of root pixels are written.
+ * 1 <= H, W <= 8192, 1 <= N <= 65535; a null required pointer or a size outside these is refused (non-zero return) before anything is
+ * launched.  Integer arithmetic and integer atomics only: results are run-to-run identical.  No entry synchronises with the host. */
+int csbsr_skeleton_topology(const uint8_t* skeleton, int32_t N, int32_t H, int32_t W, uint8_t* topo, int32_t* counts, csbsr_stream_t s);
+int csbsr_component_topology(const int32_t* labels, const uint8_t* topo, const int32_t* jlabels, int32_t N, int32_t H, int32_t W, int32_t* tacc,
+                             csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
