@@ -189,6 +189,11 @@ SIGNATURES = {
     "csbsr_component_width": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "csbsr_skeleton_topology": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "csbsr_component_topology": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "csbsr_prune_max_spur": (i32, []),
+    "csbsr_prune_steps": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "csbsr_prune_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "csbsr_prune_work_bytes": (i64, [i32, i32, i32]),
+    "csbsr_skeleton_prune": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "csbsr_head1_fwd":(i32, [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp]),
     "csbsr_head1_bwd_input": (i32, [vp, i64, vp, i32, vp, i64, i64, vp]),
     "csbsr_adam_step": (i32, [vp, vp, vp, i32, C.c_double, C.c_double, C.c_float, vp]),

@@ -9,7 +9,8 @@ returns the reference's final report, with the saved images and masks leaving th
 of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on the device; on request (``measure_threshold``) with the
 crack's area, centerline length and mean width per image, and (``min_crack_px``) with the small blobs dropped and the same numbers per
 connected crack (csrc/components.hip), (``width_radius``) with the local width at every centerline pixel (csrc/width.hip), and
-(``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip)."""
+(``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip), and (``prune_spur_px``) with the
+centerline's short side branches removed before any of that is measured (csrc/prune.hip)."""
 import csv
 import os
 
@@ -26,6 +27,7 @@ from .utils.estimate_metrics import skeleton_width, summarize_width_hist, width_
 from .utils.estimate_metrics import width_radius as _width_radius
 from .utils.estimate_metrics import skeleton_topology, summarize_topology, geodesic_length, orientation_shares, euler_number, mean_width_geodesic
 from .utils.estimate_metrics import _junction_labels, _count_roots, _component_topology, _topology_columns, TOPO_COUNTS, TOPO_ACC
+from .utils.estimate_metrics import prune_spurs, spur_length
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -430,6 +432,55 @@ def read_crack_instance_topology(path):
     return out
 
 
+SPUR_COLUMNS = ["name", "skeleton_px", "spur_px"]
+INSTANCE_SPUR_COLUMNS = ["name", "crack", "length_px", "spur_px"]
+
+
+def write_crack_spurs(path, rows):
+    """crack_spurs.csv: one row per image -- ``rows`` = (name, skeleton_px, spur_px): the centerline pixels that are left and those pruned"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(SPUR_COLUMNS)
+        for name, skel, spur in rows:
+            w.writerow([name, int(skel), int(spur)])
+
+
+def read_crack_spurs(path):
+    """what ``write_crack_spurs`` wrote: (name, skeleton_px, spur_px) per image, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != SPUR_COLUMNS:
+        raise ValueError(f"{path}: not a crack_spurs.csv header: {rows[0]}")
+    return [(name, int(skel), int(spur)) for name, skel, spur in rows[1:]]
+
+
+def write_crack_instance_spurs(path, rows):
+    """crack_instance_spurs.csv: one row per kept crack -- ``rows`` = (name, the image's ``cracks`` list with length_px and spur_px) per
+    image; ``crack`` is the numbering of crack_instances.csv"""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(INSTANCE_SPUR_COLUMNS)
+        for name, cracks in rows:
+            for j, c in enumerate(cracks):
+                w.writerow([name, j, int(c["length_px"]), int(c["spur_px"])])
+
+
+def read_crack_instance_spurs(path):
+    """what ``write_crack_instance_spurs`` wrote: (name, [dict(length_px, spur_px)]) per image, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if rows[0] != INSTANCE_SPUR_COLUMNS:
+        raise ValueError(f"{path}: not a crack_instance_spurs.csv header: {rows[0]}")
+    out = []
+    for name, j, length, spur in rows[1:]:
+        if not out or out[-1][0] != name:
+            out.append((name, []))
+        if int(j) != len(out[-1][1]):
+            raise ValueError(f"{path}: crack {j} of {name} is out of order")
+        out[-1][1].append(dict(length_px=int(length), spur_px=int(spur)))
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -613,7 +664,7 @@ def _topology_ints(sk):
 
 @torch.no_grad()
 def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
-                    width_radius=None, topology=False):
+                    width_radius=None, topology=False, prune_spur_px=None):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -665,7 +716,20 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     ``cracks`` gains endpoints, junctions, loops, links, length_geodesic_px and orientation (``crack_topology``).  The integers travel in the
     unit's one read, the per-crack columns with the unit's tables.  With ``save_dir``, crack_topology.csv (``write_crack_topology``) and,
     with ``min_crack_px``, crack_instance_topology.csv (``write_crack_instance_topology``) are written when the generator is exhausted.
-    False (the default) adds nothing: no key, no file, no launch."""
+    False (the default) adds nothing: no key, no file, no launch.
+
+    ``prune_spur_px`` = L, a whole number 1 .. 64 (it needs ``measure_threshold``; anything else is a ValueError before the model runs),
+    removes the centerline's side branches of up to L pixels before anything is measured on it (``prune_spurs``): the skeleton
+    the call reports is prune(skeletonize(R)), with ``min_crack_px`` prune(skeletonize(R)) & K -- one pruning: the skeletons of two
+    components of R are never 8-adjacent, so it is the pruning of the kept skeleton.  skeleton_px and mean_width_px, every crack's
+    length_px and mean_width_px, every ``width_radius`` and ``topology`` result and skeletons/<name> describe the pruned skeleton.  New
+    key: spur_px (int), the centerline pixels removed (over K with ``min_crack_px``), so that skeleton_px + spur_px is the call's
+    skeleton_px without the option; with ``min_crack_px`` every dict of ``cracks`` gains spur_px too.  A branch of up to L pixels that hangs
+    off a loop or a longer structure goes even where it is a real crack, and of two unequal arms at a crack's end the shorter goes when it
+    is at most L long.  The integers travel in the unit's one read, the per-crack column with the unit's tables.  With ``save_dir``,
+    crack_spurs.csv (``write_crack_spurs``) and, with ``min_crack_px``, crack_instance_spurs.csv (``write_crack_instance_spurs``) are
+    written when the generator is exhausted; crack_stats.csv and every other file keep their columns.  None (the default) adds nothing: no
+    key, no file, no launch."""
     if topology is not True and topology is not False:
         raise ValueError(f"topology is True or False, got {topology!r}")
     if topology and measure_threshold is None:
@@ -681,10 +745,15 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         if measure is None:
             raise ValueError("width_radius measures the skeleton of measure_threshold: give measure_threshold too")
         radius = _width_radius(width_radius, "width_radius")
+    spur = None
+    if prune_spur_px is not None:
+        if measure is None:
+            raise ValueError("prune_spur_px prunes the skeleton of measure_threshold: give measure_threshold too")
+        spur = spur_length(prune_spur_px, "prune_spur_px")
     saver = None
     if save_dir is not None:
         saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
-    stats, instances, widths, topologies = [], [], [], []
+    stats, instances, widths, topologies, spurs = [], [], [], [], []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -715,9 +784,15 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             for j, (o, H, W, _, _) in enumerate(layout):     # one plane per image: the stitched map, never a tile
                 plane = map_f32[o:o + H * W].view(1, H, W)
                 sk = skeletonize(plane, measure).view(-1)
+                if spur is not None:
+                    sk_all = sk
+                    sk, spur_n = prune_spurs(sk.view(1, H, W), spur)
+                    sk = sk.view(-1)
                 if min_px is None:
                     skel_u8[o:o + H * W] = sk * 255
                     px.append(torch.stack([(map_f32[o:o + H * W] - t32 > 0).sum(), sk.sum()]))
+                    if spur is not None:
+                        px[-1] = torch.cat([px[-1], spur_n.to(torch.int64)])
                     if topology:
                         topo, tints, _ = _topology_ints(sk.view(1, H, W))
                         tmaps.append(topo.view(H, W))
@@ -730,15 +805,20 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 labels = label_components(plane, measure)
                 acc = _component_sums(labels, sk)
                 keep, kept = _keep_from_sums(labels, acc, min_px, want_labels=True)
-                sk = sk * keep.view(-1)                      # skeleton(R) & K = skeleton(K)
+                sk = sk * keep.view(-1)                      # skeleton(R) & K = skeleton(K), and prune(skeleton(R)) & K = prune(skeleton(K))
                 skel_u8[o:o + H * W] = sk * 255
                 table = _table_from_sums(labels, acc, min_px)
+                if spur is not None:                         # per crack: its skeleton pixels before the pruning minus after
+                    before = _component_sums(labels, sk_all)[:, 1]
+                    table = torch.cat([table, (before - acc[:, 1])[table[:, 0].long(), table[:, 1].long() - 1].view(-1, 1)], 1)
                 if radius is not None:                       # against R: for a kept pixel the distance against K is the same
                     d2, hist = skeleton_width(plane, sk.view(1, H, W), measure, radius)
                     wd2.append(d2.view(H, W))
                     whist.append(_hist_and_widest(d2, hist))
                     table = torch.cat([table, _width_columns(table, _component_width(labels, d2), W)], 1)
                 px.append(torch.stack([keep.sum(), sk.sum(), (labels != 0).sum()]))
+                if spur is not None:
+                    px[-1] = torch.cat([px[-1], ((sk_all * keep.view(-1)).sum() - sk.sum()).view(1)])
                 if topology:                                 # of the kept skeleton; a removed component has no pixel in it
                     topo, tints, jl = _topology_ints(sk.view(1, H, W))
                     tmaps.append(topo.view(H, W))
@@ -765,14 +845,21 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 if min_px is not None:
                     rows = tables[tables[:, 0] == j]
                     cracks = crack_instances(rows[:, :8].tolist(), W)
+                    if spur is not None:
+                        for c, n in zip(cracks, rows[:, 8].tolist()):
+                            c["spur_px"] = n
                     if radius is not None:
-                        for c, (m, y, x) in zip(cracks, rows[:, 8:11].tolist()):
+                        w0 = 8 if spur is None else 9            # the spur column, where there is one, stands before the width's three
+                        for c, (m, y, x) in zip(cracks, rows[:, w0:w0 + 3].tolist()):
                             c.update(max_width_px=width_from_d2(m), widest=(y, x) if m > 0 else None)
                     if topology:
                         for c, sums in zip(cracks, rows[:, -TOPO_ACC:].tolist()):
                             c.update(crack_topology(sums, c["length_px"]))
                     item.update(removed_px=int(px[j][2]) - crack, n_cracks=len(cracks), labels=kept_labels[j], cracks=cracks)
                     instances.append((loader.names[i], cracks))
+                if spur is not None:
+                    item["spur_px"] = int(px[j][2 if min_px is None else 3])
+                    spurs.append((loader.names[i], skel, item["spur_px"]))
                 if radius is not None:
                     hist, key = whist[j, :-1], int(whist[j, -1])
                     w = summarize_width_hist(hist, radius)
@@ -802,3 +889,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             write_crack_topology(os.path.join(save_dir, "crack_topology.csv"), topologies)
             if min_px is not None:
                 write_crack_instance_topology(os.path.join(save_dir, "crack_instance_topology.csv"), instances)
+        if spur is not None:
+            write_crack_spurs(os.path.join(save_dir, "crack_spurs.csv"), spurs)
+            if min_px is not None:
+                write_crack_instance_spurs(os.path.join(save_dir, "crack_instance_spurs.csv"), instances)

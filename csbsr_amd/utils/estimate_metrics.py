@@ -533,6 +533,44 @@ def summarize_topology(counts_row, n_components, n_junctions):
             "length_geodesic_px": geodesic_length(*links), "orientation": orientation_shares(*links)}
 
 
+# ------------------------------------------------------------------------------------------- spur pruning
+PRUNE_MAX_SPUR = 64                                          # csrc/prune.hip: csbsr_prune_max_spur()
+
+
+def spur_length(spur_px, what="spur_px"):
+    """the longest side branch that is pruned, in pixels: a whole number 1 .. 64 (Python or NumPy, not a bool), anything else is a ValueError"""
+    if isinstance(spur_px, (bool, np.bool_)) or not isinstance(spur_px, (int, np.integer)) or not 1 <= spur_px <= PRUNE_MAX_SPUR:
+        raise ValueError(f"{what} is a whole number 1 .. {PRUNE_MAX_SPUR}, got {spur_px!r}")
+    return int(spur_px)
+
+
+def prune_spurs(skeleton, spur_px, return_time=False):
+    """The planes without their side branches of up to ``spur_px`` pixels (csrc/prune.hip): (pruned, removed), device tensors
+    uint8 [N, H, W] of 0 / 1 and int32 [N], for a uint8 tensor [..., H, W] that is set where it is non-zero (``skeletonize``'s, or any other);
+    removed = the set pixels of a plane minus those of its result.  Tips (end pixels with at most 3 neighbours) are peeled ``spur_px``
+    times, each step recording its number T at the pixels it deletes, and grown back in reverse order from the tips that are left: what was
+    peeled from a surviving end returns exactly, a branch that was peeled down to a junction does not, and of the arms of a fork at a
+    crack's end only the longest -- or all the longest -- return.  ``return_time`` = True adds T, uint8 [N, H, W], as a third result.  Planes
+    are independent, nothing outside a plane is set, and nothing is read by the host."""
+    L_px = spur_length(spur_px)
+    if not (torch.is_tensor(skeleton) and skeleton.dtype == torch.uint8 and skeleton.dim() >= 2):
+        raise ValueError("skeleton is a uint8 tensor [..., H, W]")
+    lib = L.load()
+    dev = skeleton.device if skeleton.is_cuda else torch.device("cuda:0")
+    H, W = int(skeleton.shape[-2]), int(skeleton.shape[-1])
+    sk = skeleton.to(dev).reshape(-1, H, W).contiguous()
+    N = sk.shape[0]
+    need = int(lib.csbsr_prune_work_bytes(N, H, W))
+    if need <= 0:
+        raise L.CsbsrHipError(f"prune_spurs: {N} planes of {H} x {W} are outside what csbsr_skeleton_prune takes")
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    out, time = (torch.empty(N, H, W, dtype=torch.uint8, device=dev) for _ in range(2))
+    removed = torch.empty(N, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("csbsr_skeleton_prune", _ptr(sk), N, H, W, L_px, _ptr(work), _ptr(time), _ptr(out), _ptr(removed), L.stream(dev))
+    return (out, removed, time) if return_time else (out, removed)
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

@@ -733,6 +733,30 @@ int csbsr_skeleton_topology(const uint8_t* skeleton, int32_t N, int32_t H, int32
 int csbsr_component_topology(const int32_t* labels, const uint8_t* topo, const int32_t* jlabels, int32_t N, int32_t H, int32_t W, int32_t* tacc,
                              csbsr_stream_t s);
 
+/* Spur pruning: the side branches of up to ``spur_px`` pixels of a binary plane go, the rest stays (csrc/prune.hip).  A pixel of
+ * ``skeleton`` is set where its byte is non-zero; everything outside the plane -- another plane of the batch too -- is clear.  With the ring,
+ * n8 and A of the topology entries, a set pixel is a tip iff A == 1 and n8 <= 3, and isolated iff n8 == 0.  Peel: X_0 = the plane; for
+ * k = 1 .. spur_px, X_k = X_(k-1) without the tips that have an 8-neighbour in X_(k-1) that is no tip, all at once; T = k at those pixels, 0
+ * where nothing was peeled.  Seeds: Z = the tips and isolated pixels of the last X, M(z) = the largest T among z's 8 neighbours.  Grow: R
+ * starts empty; for k = spur_px .. 1 it gains every pixel q with T(q) = k that has an 8-neighbour r with (r in Z and M(r) = k) or (r in R
+ * and T(r) = k + 1).  The result is the last X united with R: a run that was peeled from a surviving end comes back exactly, a branch that
+ * was peeled down to its junction does not.
+ *   csbsr_skeleton_prune   : skeleton uint8 [N][H][W].  out uint8 [N][H][W] of 0 / 1 and time uint8 [N][H][W] = T, both written at EVERY
+ *                            pixel; the skeleton, time and out are three arrays.  removed int32 [N] = the set pixels of the plane minus
+ *                            those of out, zeroed by the entry on the stream.  work: csbsr_prune_work_bytes(N, H, W) bytes of scratch (0 for
+ *                            sizes the entry refuses).  The entry enqueues all its launches; nothing is read back.
+ *   csbsr_prune_max_spur   : 64.   csbsr_prune_steps : the steps per launch of the peel and of the grow kernel.   csbsr_prune_tile : the pixels
+ *                            a workgroup owns.
+ * 1 <= H, W <= 8192, 1 <= N <= 65535, 1 <= spur_px <= 64; a null pointer or a value outside these is refused (non-zero return) before
+ * anything is launched.  Integer arithmetic and integer atomics only: results are run-to-run identical.  No entry synchronises with the
+ * host. */
+int32_t csbsr_prune_max_spur(void);
+int csbsr_prune_steps(int32_t* peel, int32_t* grow);
+int csbsr_prune_tile(int32_t* th, int32_t* tw);
+int64_t csbsr_prune_work_bytes(int32_t N, int32_t H, int32_t W);
+int csbsr_skeleton_prune(const uint8_t* skeleton, int32_t N, int32_t H, int32_t W, int32_t spur_px, void* work, uint8_t* time, uint8_t* out,
+                         int32_t* removed, csbsr_stream_t s);
+
 /* Backward of kb.up_conv1 -- ConvTranspose2d(3 -> cout, 8x8, stride 4, pad 2, no bias) + PReLU (+ residual) -- in one streaming pass over the
  * output gradient (replaces the autograd backward of /root/reference/model/modeling/kbpn.py:372-374,405-409 for that layer: PReLU backward,
  * conv_transpose2d weight gradient, slope gradient).  The pre-activation is rebuilt from the 3-channel input x [N, h, w, 8] and the forward's
