@@ -189,6 +189,9 @@ SIGNATURES = {
     "csbsr_component_width": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "csbsr_skeleton_topology": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "csbsr_component_topology": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "csbsr_branch_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "csbsr_branch_label": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "csbsr_branch_sums": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "csbsr_prune_max_spur": (i32, []),
     "csbsr_prune_steps": (i32, [C.POINTER(i32), C.POINTER(i32)]),
     "csbsr_prune_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),

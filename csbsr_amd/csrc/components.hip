@@ -47,6 +47,7 @@
 //                        skeleton pixels once (ballots + bit counts), and touches the box only where a relaxed load says it would change.
 //   component_keep     : uint8 1 where the pixel's component has >= min_px pixels; optionally the labels with the other components zeroed.
 #include "common.h"
+#include "union_find.h"
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 #define CC_TH 64                         // owned rows of a workgroup
@@ -55,41 +56,7 @@
 #define CC_MAX_SIDE 8192                 // 8192^2 = 2^26 pixels: every index and count fits an int32
 #define CC_ACC 5                         // accumulators per root: area_px, skeleton_px, x0, y1, x1
 
-#define CC_WG __HIP_MEMORY_SCOPE_WORKGROUP
-#define CC_AGENT __HIP_MEMORY_SCOPE_AGENT
-
-template <int SCOPE>
-__device__ __forceinline__ int cc_load(const int* L, int i) {
-  return __hip_atomic_load(L + i, __ATOMIC_RELAXED, SCOPE);
-}
-
-// the root of i as far as the loads show it; i strictly decreases
-template <int SCOPE>
-__device__ __forceinline__ int cc_find(const int* L, int i) {
-  for (;;) {
-    const int p = cc_load<SCOPE>(L, i);
-    if ((unsigned)p >= (unsigned)i) return i;                                       // a root (p == i); anything that is no smaller index ends the walk too
-    i = p;
-  }
-}
-
-// join the trees of the set pixels a and b; max(a, b) strictly decreases from one iteration to the next
-template <int SCOPE>
-__device__ __forceinline__ void cc_union(int* L, int a, int b) {
-  for (;;) {
-    a = cc_find<SCOPE>(L, a);
-    b = cc_find<SCOPE>(L, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);
-    if ((unsigned)old >= (unsigned)a || old == b) return;                           // a was a root and now points to b (or already did)
-    a = old;                                                                        // someone lowered the slot first: join that parent with b
-  }
-}
+// cc_load / cc_find / cc_union, shared with branches.hip: union_find.h
 
 __global__ __launch_bounds__(256) void ccl_local_kernel(const float* x, float th, int H, int W, int conn8, int* work) {
   __shared__ uint32_t bits[CC_TH * CC_TWW];

@@ -10,8 +10,10 @@ of an HBM pool (csbsr_amd/data/resident_predict.py), tiled, run and stitched on 
 crack's area, centerline length and mean width per image, and (``min_crack_px``) with the small blobs dropped and the same numbers per
 connected crack (csrc/components.hip), (``width_radius``) with the local width at every centerline pixel (csrc/width.hip), and
 (``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip), and (``prune_spur_px``) with the
-centerline's short side branches removed before any of that is measured (csrc/prune.hip)."""
+centerline's short side branches removed before any of that is measured (csrc/prune.hip), and (``branches``) with one row per centerline
+segment between junctions (csrc/branches.hip)."""
 import csv
+import gc
 import os
 
 import numpy as np
@@ -28,6 +30,7 @@ from .utils.estimate_metrics import width_radius as _width_radius
 from .utils.estimate_metrics import skeleton_topology, summarize_topology, geodesic_length, orientation_shares, euler_number, mean_width_geodesic
 from .utils.estimate_metrics import _junction_labels, _count_roots, _component_topology, _topology_columns, TOPO_COUNTS, TOPO_ACC
 from .utils.estimate_metrics import prune_spurs, spur_length
+from .utils.estimate_metrics import label_branches, branch_table, branch_kinds, BRANCH_COLUMNS, BRANCH_KINDS, _SQRT2
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -481,6 +484,91 @@ def read_crack_instance_spurs(path):
     return out
 
 
+BRANCH_CSV_COLUMNS = ["name", "branch", "y", "x", "kind", "px", "ends", "attach", "node_a", "node_b", "h", "v", "d_se", "d_sw", "length_geodesic_px",
+                      "share_h", "share_v", "share_se", "share_sw", "y0", "x0", "y1", "x1"]
+BRANCH_CSV_OPTIONAL = ["crack", "max_width_px", "min_width_px"]      # behind the others, each only where the branches carry the key
+
+
+def crack_branches(rows, W, crack_of_label=None):
+    """the ``branches`` list of ``predict_dataset`` from the host rows of ``branch_table`` (``BRANCH_COLUMNS``, and the two width columns
+    where the table has them): dict(y, x, kind, px, ends, attach, nodes, links, length_geodesic_px, orientation, bbox) per branch, (y, x)
+    the branch's first pixel in raster order.  ``crack_of_label`` (component label -> index into ``cracks``) adds crack; the width columns
+    add max_width_px and min_width_px (``width_from_d2``)."""
+    c = {k: j for j, k in enumerate(BRANCH_COLUMNS)}
+    rows = np.asarray(rows, np.int64).reshape(-1, np.shape(rows)[1] if np.ndim(rows) == 2 else len(BRANCH_COLUMNS))
+    nc = len(BRANCH_COLUMNS)
+    # the fp64 columns for all rows at once: the arithmetic of geodesic_length and orientation_shares, element by element
+    lk = rows[:, [c["h"], c["v"], c["d_se"], c["d_sw"]]]
+    length = np.asarray(geodesic_length(lk[:, 0], lk[:, 1], lk[:, 2], lk[:, 3]), np.float64).reshape(-1)
+    parts = lk.astype(np.float64) * np.array([1.0, 1.0, _SQRT2, _SQRT2])
+    share = np.divide(parts, length[:, None], out=np.zeros_like(parts), where=length[:, None] > 0)
+    wide = rows.shape[1] > nc
+    width = width_from_d2(rows[:, nc:nc + 2]).tolist() if wide else None
+    kinds = branch_kinds(rows)
+    col = lambda *names: rows[:, [c[k] for k in names]].tolist()
+    ys, xs = np.divmod(rows[:, c["label"]] - 1, W)
+    # Five containers per branch, thousands per image: each batch of 700 makes the cyclic collector run, and every tenth and hundredth run
+    # walks the older generations -- the whole heap of a loaded model, 60 ms measured for one such walk against 2 ms for this list.  None
+    # of these objects is part of a cycle, so the collector is paused while they are built.
+    paused = gc.isenabled()
+    gc.disable()
+    try:
+        out = [dict(y=y, x=x, kind=kind, px=px, ends=end, attach=att, nodes=tuple(nodes), links=tuple(links), length_geodesic_px=n,
+                    orientation=tuple(sh), bbox=tuple(box))
+               for y, x, kind, (px, end, att), nodes, links, n, sh, box in zip(ys.tolist(), xs.tolist(), kinds, col("px", "end", "attach"),
+                                                                                col("node_a", "node_b"), lk.tolist(), length.tolist(), share.tolist(),
+                                                                                col("y0", "x0", "y1", "x1"))]
+    finally:
+        if paused:
+            gc.enable()
+    if crack_of_label is not None:
+        for d, lab in zip(out, rows[:, c["crack"]].tolist()):
+            d["crack"] = crack_of_label[lab]
+    if wide:
+        for d, (hi, lo) in zip(out, width):
+            d.update(max_width_px=hi, min_width_px=lo)
+    return out
+
+
+def write_crack_branches(path, rows):
+    """crack_branches.csv: one row per branch -- ``rows`` = (name, the image's ``branches`` list) per image; ``branch`` numbers an image's
+    branches in raster order of their first pixel, ``crack`` (with ``min_crack_px``) is the numbering of crack_instances.csv"""
+    first = next((b[0] for _, b in rows if b), {})
+    optional = [k for k in BRANCH_CSV_OPTIONAL if k in first]
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(BRANCH_CSV_COLUMNS + optional)
+        for name, branches in rows:
+            for j, b in enumerate(branches):
+                w.writerow([name, j, int(b["y"]), int(b["x"]), b["kind"], int(b["px"]), int(b["ends"]), int(b["attach"])] + [int(k) for k in b["nodes"]]
+                           + [int(k) for k in b["links"]] + [repr(float(b["length_geodesic_px"]))] + [repr(float(k)) for k in b["orientation"]]
+                           + [int(k) for k in b["bbox"]] + [int(b[k]) if k == "crack" else repr(float(b[k])) for k in optional])
+
+
+def read_crack_branches(path):
+    """what ``write_crack_branches`` wrote: (name, [dict]) per image that has a branch, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    n = len(BRANCH_CSV_COLUMNS)
+    optional = rows[0][n:]
+    if rows[0][:n] != BRANCH_CSV_COLUMNS or optional != [k for k in BRANCH_CSV_OPTIONAL if k in optional]:
+        raise ValueError(f"{path}: not a crack_branches.csv header: {rows[0]}")
+    out = []
+    for r in rows[1:]:
+        if not out or out[-1][0] != r[0]:
+            out.append((r[0], []))
+        if int(r[1]) != len(out[-1][1]):
+            raise ValueError(f"{path}: branch {r[1]} of {r[0]} is out of order")
+        if r[4] not in BRANCH_KINDS:
+            raise ValueError(f"{path}: {r[4]!r} is no branch kind")
+        d = dict(y=int(r[2]), x=int(r[3]), kind=r[4], px=int(r[5]), ends=int(r[6]), attach=int(r[7]), nodes=(int(r[8]), int(r[9])),
+                 links=tuple(int(v) for v in r[10:14]), length_geodesic_px=float(r[14]), orientation=tuple(float(v) for v in r[15:19]),
+                 bbox=tuple(int(v) for v in r[19:23]))
+        d.update({k: int(v) if k == "crack" else float(v) for k, v in zip(optional, r[n:])})
+        out[-1][1].append(d)
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -664,7 +752,7 @@ def _topology_ints(sk):
 
 @torch.no_grad()
 def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
-                    width_radius=None, topology=False, prune_spur_px=None):
+                    width_radius=None, topology=False, prune_spur_px=None, branches=False):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -729,11 +817,27 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     is at most L long.  The integers travel in the unit's one read, the per-crack column with the unit's tables.  With ``save_dir``,
     crack_spurs.csv (``write_crack_spurs``) and, with ``min_crack_px``, crack_instance_spurs.csv (``write_crack_instance_spurs``) are
     written when the generator is exhausted; crack_stats.csv and every other file keep their columns.  None (the default) adds nothing: no
-    key, no file, no launch."""
+    key, no file, no launch.
+
+    ``branches`` = True (only True and False are accepted, and True needs ``topology`` = True; anything else is a ValueError before the
+    model runs) adds the branch table (``label_branches``, ``branch_table``) of the skeleton the call reports -- pruned with
+    ``prune_spur_px``, kept with ``min_crack_px`` --: one row per centerline segment between junctions.  New keys: n_branches; branch_kinds
+    (a dict over ``BRANCH_KINDS`` of counts); longest_branch_px (the largest length_geodesic_px of a branch that is not isolated, as in
+    ``summarize_branches``); branch_map (device int32 [H, W], the branch
+    labels); branches, a list in raster order of the first pixel of dict(y, x, kind, px, ends, attach, nodes=(a, b), links,
+    length_geodesic_px, orientation, bbox) (``crack_branches``) -- with ``min_crack_px`` each also carries crack, the index into ``cracks``,
+    and every dict of ``cracks`` gains n_branches; with ``width_radius`` each carries max_width_px and min_width_px.  A branch that
+    touches three or more junction clusters names only the smallest and the largest in nodes, and its attach exceeds 2.  The branch rows
+    travel in a tensor of their own, one more read per unit.  With ``save_dir``, crack_branches.csv (``write_crack_branches``) is written
+    when the generator is exhausted; no other file gains a column.  False (the default) adds nothing: no key, no file, no launch."""
     if topology is not True and topology is not False:
         raise ValueError(f"topology is True or False, got {topology!r}")
     if topology and measure_threshold is None:
         raise ValueError("topology describes the skeleton of measure_threshold: give measure_threshold too")
+    if branches is not True and branches is not False:
+        raise ValueError(f"branches is True or False, got {branches!r}")
+    if branches and not topology:
+        raise ValueError("branches are the segments of the topology's link graph: give topology=True (and measure_threshold) too")
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
     min_px = None
     if min_crack_px is not None:
@@ -753,7 +857,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     saver = None
     if save_dir is not None:
         saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
-    stats, instances, widths, topologies, spurs = [], [], [], [], []
+    stats, instances, widths, topologies, spurs, branch_rows = [], [], [], [], [], []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -776,7 +880,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         kernels = torch.cat(kernels)
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
-        extra, px, kept_labels, tables, wd2, whist, tmaps = [], None, [], None, [], [], []
+        extra, px, kept_labels, tables, wd2, whist, tmaps, bmaps, btables = [], None, [], None, [], [], [], [], []
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
@@ -794,13 +898,19 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     if spur is not None:
                         px[-1] = torch.cat([px[-1], spur_n.to(torch.int64)])
                     if topology:
-                        topo, tints, _ = _topology_ints(sk.view(1, H, W))
+                        topo, tints, jl = _topology_ints(sk.view(1, H, W))
                         tmaps.append(topo.view(H, W))
                         px[-1] = torch.cat([px[-1], tints])
+                    d2 = None
                     if radius is not None:
                         d2, hist = skeleton_width(plane, sk.view(1, H, W), measure, radius)
                         wd2.append(d2.view(H, W))
                         whist.append(_hist_and_widest(d2, hist))
+                    if branches:
+                        bl = label_branches(topo)
+                        bmaps.append(bl.view(H, W))
+                        btables.append(branch_table(bl, topo, jl, None, d2))
+                        btables[-1][:, 0] = j
                     continue
                 labels = label_components(plane, measure)
                 acc = _component_sums(labels, sk)
@@ -808,6 +918,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 sk = sk * keep.view(-1)                      # skeleton(R) & K = skeleton(K), and prune(skeleton(R)) & K = prune(skeleton(K))
                 skel_u8[o:o + H * W] = sk * 255
                 table = _table_from_sums(labels, acc, min_px)
+                d2 = None
                 if spur is not None:                         # per crack: its skeleton pixels before the pruning minus after
                     before = _component_sums(labels, sk_all)[:, 1]
                     table = torch.cat([table, (before - acc[:, 1])[table[:, 0].long(), table[:, 1].long() - 1].view(-1, 1)], 1)
@@ -824,12 +935,18 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     tmaps.append(topo.view(H, W))
                     px[-1] = torch.cat([px[-1], tints])
                     table = torch.cat([table, _topology_columns(table, _component_topology(labels, topo, jl))], 1)
+                if branches:                                 # a tensor of their own: the topology columns stay the table's last
+                    bl = label_branches(topo)
+                    bmaps.append(bl.view(H, W))
+                    btables.append(branch_table(bl, topo, jl, kept, d2))
+                    btables[-1][:, 0] = j
                 table[:, 0] = j                              # the image within the unit
                 tables.append(table)
                 kept_labels.append(kept.view(H, W))
             px = torch.stack(px).cpu().tolist()              # the unit's integers in one read
             tables = torch.cat(tables).cpu().numpy() if min_px is not None else None         # and the unit's tables in one more
             whist = torch.stack(whist).cpu().numpy() if radius is not None else None         # the unit's histograms (and widest keys) in one
+            btables = torch.cat(btables).cpu().numpy() if branches else None                 # the unit's branch rows in one more
             extra = [skel_u8]
         if saver is not None:
             planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
@@ -874,6 +991,19 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     tp["mean_width_geodesic_px"] = mean_width_geodesic(crack, tp["length_geodesic_px"])
                     item.update(tp, topology_map=tmaps[j])
                     topologies.append((loader.names[i], tp))
+                if branches:
+                    rows = btables[btables[:, 0] == j]
+                    of_label = {c["y"] * W + c["x"] + 1: k for k, c in enumerate(item["cracks"])} if min_px is not None else None
+                    blist = crack_branches(rows, W, of_label)
+                    kinds = [b["kind"] for b in blist]
+                    item.update(n_branches=len(blist), branch_kinds={k: kinds.count(k) for k in BRANCH_KINDS},
+                                longest_branch_px=max([b["length_geodesic_px"] for b in blist if b["kind"] != "isolated"], default=0.0),
+                                branch_map=bmaps[j], branches=blist)
+                    if min_px is not None:
+                        per_crack = np.bincount([b["crack"] for b in blist], minlength=len(item["cracks"])).tolist()
+                        for c, n in zip(item["cracks"], per_crack):
+                            c["n_branches"] = n
+                    branch_rows.append((loader.names[i], blist))
             yield item
     if saver is not None:
         saver.drain()
@@ -889,6 +1019,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             write_crack_topology(os.path.join(save_dir, "crack_topology.csv"), topologies)
             if min_px is not None:
                 write_crack_instance_topology(os.path.join(save_dir, "crack_instance_topology.csv"), instances)
+        if branches:
+            write_crack_branches(os.path.join(save_dir, "crack_branches.csv"), branch_rows)
         if spur is not None:
             write_crack_spurs(os.path.join(save_dir, "crack_spurs.csv"), spurs)
             if min_px is not None:

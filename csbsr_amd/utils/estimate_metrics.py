@@ -571,6 +571,134 @@ def prune_spurs(skeleton, spur_px, return_time=False):
     return (out, removed, time) if return_time else (out, removed)
 
 
+# ------------------------------------------------------------------------------------------- crack branches
+BRANCH_ACC = 12                                              # csrc/branches.hip: the accumulators per root pixel, and two more with a d2 map
+BRANCH_COLUMNS = ("plane", "label", "crack", "px", "end", "isolated", "attach", "h", "v", "d_se", "d_sw", "node_a", "node_b", "y0", "x0", "y1",
+                  "x1")
+BRANCH_WIDTH_COLUMNS = ("max_d2", "min_d2")                  # behind BRANCH_COLUMNS when ``branch_table`` is given a d2 map
+BRANCH_KINDS = ("isolated", "free", "ring", "terminal", "self_loop", "link")
+
+
+def _topo(topo):
+    if not (torch.is_tensor(topo) and topo.dtype == torch.uint8 and topo.dim() == 3):
+        raise ValueError("topo is the uint8 tensor [N, H, W] of skeleton_topology")
+    return (topo if topo.is_cuda else topo.to("cuda:0")).contiguous()
+
+
+def label_branches(topo):
+    """The branches of ``skeleton_topology``'s topo (csrc/branches.hip): int32 device tensor [N, H, W].  A branch pixel is a set
+    pixel that is no junction (class 1, 2 or 3), a branch a connected component of the branch pixels under the owned links between two of
+    them -- the centerline segments between junctions; an isolated pixel is a branch of one pixel.  The value is 0 at clear and at junction
+    pixels, else 1 + min(y W + x) over the pixel's branch: defined by a minimum, so two runs give the same bits.  Planes are independent."""
+    topo = _topo(topo)
+    L.load()
+    N, H, W = topo.shape
+    work, blabels = (torch.empty(N, H, W, dtype=torch.int32, device=topo.device) for _ in range(2))
+    with torch.cuda.device(topo.device):
+        L.call("csbsr_branch_label", _ptr(topo), N, H, W, _ptr(work), _ptr(blabels), L.stream(topo.device))
+    return blabels
+
+
+def _plane_like(t, like, what):
+    if not (torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == tuple(like.shape)):
+        raise ValueError(f"{what} is an int32 tensor {tuple(like.shape)}, one value per branch label")
+    return t.to(like.device).contiguous()
+
+
+def _branch_sums(blabels, topo, jlabels=None, d2=None):
+    """the accumulators of csbsr_branch_sums, int32 [N, 12 or 14, H * W]: only the slots of root pixels hold values"""
+    N, H, W = blabels.shape
+    bacc = torch.empty(N, BRANCH_ACC + (0 if d2 is None else 2), H * W, dtype=torch.int32, device=blabels.device)
+    with torch.cuda.device(blabels.device):
+        L.call("csbsr_branch_sums", _ptr(blabels), _ptr(topo), None if jlabels is None else _ptr(jlabels), None if d2 is None else _ptr(d2),
+               N, H, W, _ptr(bacc), L.stream(blabels.device))
+    return bacc
+
+
+def branch_table(blabels, topo, jlabels=None, labels=None, d2=None):
+    """One row per branch of ``label_branches``' labels: int32 device tensor [M, 17] = ``BRANCH_COLUMNS``, in raster order of the branch's
+    first pixel, plane by plane -- sorted by (plane, label).  px: the branch's pixels; end: its end pixels (class 2); isolated: 1 for a
+    class-1 pixel; h, v, d_se, d_sw: its links of each kind, those between two of its pixels and those that attach it to a junction pixel
+    (whichever end owns the link), so that ``geodesic_length`` runs from junction pixel centre to junction pixel centre; attach: its attach
+    links; node_a, node_b: the smallest and largest value of ``jlabels`` (the junction clusters, ``label_components`` of the class-4 mask)
+    among the junction pixels it attaches to -- 0 and 0 without an attach link or without ``jlabels``; a branch that touches three or more
+    clusters reports only these two, and its attach exceeds 2 --; (y0, x0, y1, x1): the inclusive box.  crack is ``labels`` (e.g. the
+    component labels of ``label_components``) at the branch's first pixel, 0 without.  With ``d2`` (``skeleton_width``'s) two more columns,
+    ``BRANCH_WIDTH_COLUMNS``: the largest d2 and the smallest d2 > 0 over the branch's pixels (0 if none)."""
+    if not (torch.is_tensor(blabels) and blabels.is_cuda and blabels.dtype == torch.int32 and blabels.dim() == 3):
+        raise ValueError("blabels is the int32 device tensor [N, H, W] of label_branches")
+    L.load()
+    blabels = blabels.contiguous()
+    N, H, W = blabels.shape
+    if not (torch.is_tensor(topo) and topo.dtype == torch.uint8 and tuple(topo.shape) == (N, H, W)):
+        raise ValueError("topo is the uint8 tensor [N, H, W] of skeleton_topology, one value per branch label")
+    topo = topo.to(blabels.device).contiguous()
+    jlabels, labels, d2 = (None if t is None else _plane_like(t, blabels, what) for t, what in ((jlabels, "jlabels"), (labels, "labels"), (d2, "d2")))
+    bacc = _branch_sums(blabels, topo, jlabels, d2)
+    flat = blabels.view(N, H * W)
+    roots = torch.nonzero(flat == torch.arange(1, H * W + 1, dtype=torch.int32, device=blabels.device))
+    n, i = roots[:, 0], roots[:, 1]
+    v = bacc[n, :, i].to(torch.int64)                        # [M, 12 or 14]
+    crack = labels.view(N, H * W)[n, i].to(torch.int64) if labels is not None else torch.zeros_like(i)
+    isolated = ((topo.view(N, H * W)[n, i] & 7) == TOPO_ISOLATED).to(torch.int64)
+    cols = [n, i + 1, crack, v[:, 0], v[:, 1], isolated] + [v[:, k] for k in range(2, 9)] + [torch.div(i, W, rounding_mode="floor"), v[:, 9], v[:, 10],
+                                                                                            v[:, 11]]
+    return torch.stack(cols + ([v[:, 12], v[:, 13]] if d2 is not None else []), 1).to(torch.int32)
+
+
+def branch_kind(end, attach, node_a, node_b, isolated):
+    """what a branch is, from its row of ``branch_table``: 'isolated' (a class-1 pixel), 'free' (no attach link and two ends: a crack without
+    a junction), 'ring' (no attach link and no end: a closed loop without a junction), 'terminal' (an end and an attach link: a dead end),
+    'self_loop' (no end, attached, and node_a == node_b: it leaves and re-enters one junction cluster) or 'link' (the rest: it joins two
+    junction clusters).  The node columns need the table's ``jlabels``."""
+    end, attach = int(end), int(attach)
+    if int(isolated):
+        return "isolated"
+    if attach == 0 and end == 2:
+        return "free"
+    if attach == 0 and end == 0:
+        return "ring"
+    if end >= 1 and attach >= 1:
+        return "terminal"
+    if end == 0 and attach >= 1 and int(node_a) == int(node_b):
+        return "self_loop"
+    return "link"
+
+
+def _branch_rows(rows):
+    r = _host_ints(rows).astype(np.int64)
+    if r.ndim != 2 or r.shape[1] not in (len(BRANCH_COLUMNS), len(BRANCH_COLUMNS) + len(BRANCH_WIDTH_COLUMNS)):
+        raise ValueError(f"branch rows are [M, {len(BRANCH_COLUMNS)}] or [M, {len(BRANCH_COLUMNS) + len(BRANCH_WIDTH_COLUMNS)}] integers "
+                         f"(branch_table), got shape {r.shape}")
+    return r
+
+
+def branch_kinds(rows):
+    """the kind (``branch_kind``) of every row of ``branch_table``, a list of strings: the truth table on whole columns"""
+    r = _branch_rows(rows)
+    c = {k: j for j, k in enumerate(BRANCH_COLUMNS)}
+    end, attach, same = r[:, c["end"]], r[:, c["attach"]], r[:, c["node_a"]] == r[:, c["node_b"]]
+    k = np.select([r[:, c["isolated"]] != 0, (attach == 0) & (end == 2), (attach == 0) & (end == 0), (end >= 1) & (attach >= 1),
+                   (end == 0) & (attach >= 1) & same], [0, 1, 2, 3, 4], 5)
+    return [BRANCH_KINDS[j] for j in k.tolist()]
+
+
+def summarize_branches(rows):
+    """The branch figures of one plane (or of any set of rows of ``branch_table``), fp64 on the host: n_branches, branch_kinds (a dict over
+    ``BRANCH_KINDS`` of counts), and over the geodesic lengths (``geodesic_length`` of h, v, d_se, d_sw) of the branches that are not
+    isolated: longest_branch_px, median_branch_px (the element of zero-based rank (n - 1) // 2 of the sorted lengths) and total_branch_px.
+    No such branch: the three lengths are 0.0."""
+    r = _branch_rows(rows)
+    c = {k: j for j, k in enumerate(BRANCH_COLUMNS)}
+    kinds = branch_kinds(r)
+    out = {"n_branches": int(r.shape[0]), "branch_kinds": {k: kinds.count(k) for k in BRANCH_KINDS}}
+    length = np.sort(np.asarray(geodesic_length(r[:, c["h"]], r[:, c["v"]], r[:, c["d_se"]], r[:, c["d_sw"]]), np.float64)[r[:, c["isolated"]] == 0])
+    n = int(length.size)
+    out.update(longest_branch_px=float(length[-1]) if n else 0.0, median_branch_px=float(length[(n - 1) // 2]) if n else 0.0,
+               total_branch_px=float(length.sum()) if n else 0.0)
+    return out
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

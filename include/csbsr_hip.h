@@ -733,6 +733,32 @@ int csbsr_skeleton_topology(const uint8_t* skeleton, int32_t N, int32_t H, int32
 int csbsr_component_topology(const int32_t* labels, const uint8_t* topo, const int32_t* jlabels, int32_t N, int32_t H, int32_t W, int32_t* tacc,
                              csbsr_stream_t s);
 
+/* Crack branches: one label per centerline segment between junctions, and one set of sums per branch (csrc/branches.hip).
+ * ``topo`` is csbsr_skeleton_topology's byte plane.  A branch pixel has class 1, 2 or 3 (bits 0-2), a junction pixel class 4.  An inner link
+ * is an owned E / S / SE / SW link (bits 4 .. 7) whose two ends are branch pixels, an attach link one with exactly one junction end, a cluster
+ * link one between two junction pixels.  A branch is a connected component of the branch pixels under the inner links; an isolated pixel
+ * (class 1) is a branch of one pixel.  A link bit whose other end lies outside the plane or is clear is ignored.
+ *   csbsr_branch_tile  : the pixels one workgroup of the labelling owns, rows and columns (the seams of the merge launch).
+ *   csbsr_branch_label : topo uint8 [N][H][W].  blabels int32 [N][H][W], written at EVERY pixel: 0 at clear and at junction pixels, else
+ *                        1 + the smallest linear index y W + x of the pixel's branch -- a minimum: the bits do not depend on scheduling.
+ *                        work int32 [N][H][W] of scratch, another array than blabels.
+ *   csbsr_branch_sums  : blabels as above, topo as above, jlabels int32 [N][H][W] = csbsr_ccl_label's labels (8-connected) of the junction
+ *                        pixels, or NULL, d2 int32 [N][H][W] of csbsr_skeleton_width, or NULL.  bacc int32 [N][K][H W], K = 12 without d2
+ *                        and 14 with it, indexed by ROOT pixel i = blabel - 1; ONLY the slots of root pixels are written.  Slots:
+ *                          0 px, 1 end (class-2 pixels), 2 attach (attach links),
+ *                          3 h, 4 v, 5 d_se, 6 d_sw : the inner plus attach links of each kind -- an attach link counts for the branch
+ *                                                     of its non-junction end, whichever end owns it,
+ *                          7 node_a, 8 node_b       : the smallest and the largest jlabels value among the junction pixels the branch
+ *                                                     attaches to (0 and 0 without an attach link or without jlabels),
+ *                          9 x0, 10 y1, 11 x1       : the inclusive box (y0 is the root's own row),
+ *                          12 max_d2, 13 min_d2     : the largest d2, and the smallest d2 > 0, over the branch's pixels (0 if none).
+ * 1 <= H, W <= 8192, 1 <= N <= 65535; a null required pointer or a size outside these is refused (non-zero return) before anything is
+ * launched.  Integer arithmetic and integer atomics only: results are run-to-run identical.  No entry synchronises with the host. */
+int csbsr_branch_tile(int32_t* th, int32_t* tw);
+int csbsr_branch_label(const uint8_t* topo, int32_t N, int32_t H, int32_t W, int32_t* work, int32_t* blabels, csbsr_stream_t s);
+int csbsr_branch_sums(const int32_t* blabels, const uint8_t* topo, const int32_t* jlabels, const int32_t* d2, int32_t N, int32_t H, int32_t W,
+                      int32_t* bacc, csbsr_stream_t s);
+
 /* Spur pruning: the side branches of up to ``spur_px`` pixels of a binary plane go, the rest stays (csrc/prune.hip).  A pixel of
  * ``skeleton`` is set where its byte is non-zero; everything outside the plane -- another plane of the batch too -- is clear.  With the ring,
  * n8 and A of the topology entries, a set pixel is a tip iff A == 1 and n8 <= 3, and isolated iff n8 == 0.  Peel: X_0 = the plane; for
