@@ -11,9 +11,11 @@ crack's area, centerline length and mean width per image, and (``min_crack_px``)
 connected crack (csrc/components.hip), (``width_radius``) with the local width at every centerline pixel (csrc/width.hip), and
 (``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip), and (``prune_spur_px``) with the
 centerline's short side branches removed before any of that is measured (csrc/prune.hip), and (``branches``) with one row per centerline
-segment between junctions (csrc/branches.hip)."""
+segment between junctions (csrc/branches.hip), and (``polylines``) with every segment's pixels in order from end to end
+(csrc/polylines.hip)."""
 import csv
 import gc
+import math
 import os
 
 import numpy as np
@@ -31,6 +33,7 @@ from .utils.estimate_metrics import skeleton_topology, summarize_topology, geode
 from .utils.estimate_metrics import _junction_labels, _count_roots, _component_topology, _topology_columns, TOPO_COUNTS, TOPO_ACC
 from .utils.estimate_metrics import prune_spurs, spur_length
 from .utils.estimate_metrics import label_branches, branch_table, branch_kinds, BRANCH_COLUMNS, BRANCH_KINDS, _SQRT2
+from .utils.estimate_metrics import order_branches, branch_polylines, arc_position, _diag_along
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -569,6 +572,99 @@ def read_crack_branches(path):
     return out
 
 
+POLYLINE_CSV_COLUMNS = ["name", "branch", "i", "y", "x", "s_px"]
+POLYLINE_CSV_OPTIONAL = ["width_px"]                        # behind the others, only where the branches carry width_profile_px
+
+
+def crack_polylines(branches, chain, points, widths=False):
+    """adds the polyline keys of ``predict_dataset`` to the dicts of one image's ``branches`` list: ``chain`` [M] of 0 / 1 and ``points`` int
+    [P_chain, 4] (``ORDER_COLUMNS``) are the host copies of ``branch_polylines``' results for the image, the chains' spans one after the
+    other in the list's order.  New keys: chain (bool), points (NumPy int32 [px, 2], y then x, in order; empty for a branch that is no
+    chain), start, stop, arc_px, chord_px, tortuosity, direction_deg -- the values of ``polyline_stats``, for all branches at once; a chain
+    with as many inner links as pixels is a cycle (a path has px - 1) -- and with ``widths`` width_profile_px (fp64 [px], ``width_from_d2``
+    of the d2 column)."""
+    points = np.asarray(points, np.int64).reshape(-1, 4)
+    chain = np.asarray(chain).astype(bool).reshape(-1)
+    px = np.array([b["px"] for b in branches], np.int64)
+    if chain.shape != px.shape:
+        raise ValueError(f"{chain.size} chain flags for {px.size} branches")
+    n = np.where(chain, px, 0)
+    off = np.concatenate([np.zeros(1, np.int64), np.cumsum(n)])
+    if off[-1] != points.shape[0]:
+        raise ValueError(f"{points.shape[0]} points for chains of {int(off[-1])} pixels")
+    yx = points[:, :2].astype(np.int32)
+    some = n > 0
+    a, z = points[off[:-1][some]], points[off[1:][some] - 1]                         # the first and the last point of every chain
+    arc = np.atleast_1d(arc_position(n[some] - 1, z[:, 2]))                          # the last point's diag counts the diagonal links
+    dy, dx = z[:, 0] - a[:, 0], z[:, 1] - a[:, 1]
+    chord = np.sqrt((dy * dy + dx * dx).astype(np.float64))
+    ratio = np.divide(arc, chord, out=np.zeros_like(arc), where=chord > 0)
+    width = np.atleast_1d(width_from_d2(points[:, 3])).astype(np.float64) if widths else None
+    stats = iter(zip(a[:, :2].tolist(), z[:, :2].tolist(), arc.tolist(), chord.tolist(), ratio.tolist(), dy.tolist(), dx.tolist()))
+    for b, c, o0, o1 in zip(branches, chain.tolist(), off[:-1].tolist(), off[1:].tolist()):
+        b["chain"] = c
+        if o1 > o0:
+            p0, p1, s, ch, r, ddy, ddx = next(stats)
+            cycle = sum(b["links"]) - b["attach"] == b["px"]
+            b.update(start=tuple(p0), stop=tuple(p1), arc_px=s, chord_px=ch, tortuosity=None if ch == 0 or cycle else r,
+                     direction_deg=None if ch == 0 else math.degrees(math.atan2(ddy, ddx)) % 180.0)
+        else:
+            b.update(start=None, stop=None, arc_px=0.0, chord_px=0.0, tortuosity=None, direction_deg=None)
+        b["points"] = yx[o0:o1]
+        if widths:
+            b["width_profile_px"] = width[o0:o1]
+
+
+def write_crack_polylines(path, rows):
+    """crack_polylines.csv: one row per ordered pixel -- ``rows`` = (name, the image's ``branches`` list with the polyline keys) per image;
+    ``branch`` is the numbering of crack_branches.csv, i the pixel's position along the branch, s_px its ``arc_position``, width_px (with
+    ``width_radius``) its local width.  A branch that is no chain has no row."""
+    first = next((b[0] for _, b in rows if b), {})
+    wide = "width_profile_px" in first
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(POLYLINE_CSV_COLUMNS + (POLYLINE_CSV_OPTIONAL if wide else []))
+        for name, branches in rows:
+            for j, b in enumerate(branches):
+                pts = np.asarray(b["points"]).reshape(-1, 2)
+                s = np.atleast_1d(arc_position(np.arange(pts.shape[0]), _diag_along(pts))) if pts.shape[0] else []
+                for i, (y, x) in enumerate(pts.tolist()):
+                    w.writerow([name, j, i, y, x, repr(float(s[i]))] + ([repr(float(b["width_profile_px"][i]))] if wide else []))
+
+
+def read_crack_polylines(path):
+    """what ``write_crack_polylines`` wrote: (name, [dict(branch, points int32 [px, 2], s_px fp64 [px] and, where the file has it, width_px
+    fp64 [px])]) per image that has an ordered pixel, the branches in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    n = len(POLYLINE_CSV_COLUMNS)
+    if rows[0][:n] != POLYLINE_CSV_COLUMNS or rows[0][n:] not in ([], POLYLINE_CSV_OPTIONAL):
+        raise ValueError(f"{path}: not a crack_polylines.csv header: {rows[0]}")
+    wide = len(rows[0]) > n
+    out = []
+    for r in rows[1:]:
+        if not out or out[-1][0] != r[0]:
+            out.append((r[0], []))
+        if not out[-1][1] or out[-1][1][-1]["branch"] != int(r[1]):
+            if out[-1][1] and out[-1][1][-1]["branch"] > int(r[1]):
+                raise ValueError(f"{path}: branch {r[1]} of {r[0]} is out of order")
+            out[-1][1].append(dict(branch=int(r[1]), points=[], s_px=[], **({"width_px": []} if wide else {})))
+        d = out[-1][1][-1]
+        if int(r[2]) != len(d["points"]):
+            raise ValueError(f"{path}: point {r[2]} of branch {r[1]} of {r[0]} is out of order")
+        d["points"].append((int(r[3]), int(r[4])))
+        d["s_px"].append(float(r[5]))
+        if wide:
+            d["width_px"].append(float(r[6]))
+    for _, branches in out:
+        for d in branches:
+            d["points"] = np.array(d["points"], np.int32).reshape(-1, 2)
+            d["s_px"] = np.array(d["s_px"], np.float64)
+            if wide:
+                d["width_px"] = np.array(d["width_px"], np.float64)
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -750,9 +846,19 @@ def _topology_ints(sk):
     return topo, ints, jl
 
 
+def _order_into(bl, topo, d2, rmaps, btables, ptables):
+    """the polylines of one image's branch labels: its rank map, the chain flag behind the image's branch rows, its ordered points"""
+    H, W = bl.shape[-2:]
+    rank, diag = order_branches(bl, topo)
+    chain, _, points = branch_polylines(bl, rank, diag, d2)
+    rmaps.append(rank.view(H, W))
+    btables[-1] = torch.cat([btables[-1], chain.to(torch.int32).view(-1, 1)], 1)
+    ptables.append(points)
+
+
 @torch.no_grad()
 def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
-                    width_radius=None, topology=False, prune_spur_px=None, branches=False):
+                    width_radius=None, topology=False, prune_spur_px=None, branches=False, polylines=False):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -829,7 +935,20 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     and every dict of ``cracks`` gains n_branches; with ``width_radius`` each carries max_width_px and min_width_px.  A branch that
     touches three or more junction clusters names only the smallest and the largest in nodes, and its attach exceeds 2.  The branch rows
     travel in a tensor of their own, one more read per unit.  With ``save_dir``, crack_branches.csv (``write_crack_branches``) is written
-    when the generator is exhausted; no other file gains a column.  False (the default) adds nothing: no key, no file, no launch."""
+    when the generator is exhausted; no other file gains a column.  False (the default) adds nothing: no key, no file, no launch.
+
+    ``polylines`` = True (only True and False are accepted, and True needs ``branches`` = True; anything else is a ValueError before the
+    model runs) orders the pixels of every branch from end to end (``order_branches``, ``branch_polylines``), on the skeleton
+    the call reports, as ``branches`` does.  New keys: n_chains (the branches that are ordered); unordered_branch_px (the pixels of the
+    others: a branch through a full 2 x 2 quad is no chain and is not ordered); rank_map (device int32 [H, W], the position of every pixel
+    along its branch, -1 where there is none).  Every dict of ``branches`` gains chain; start and stop, (y, x) -- a path starts at its end
+    with the smaller linear index, a closed chain at its first pixel in raster order --; arc_px, the chain-code length of the inner links between
+    them (it counts inner links only: length_geodesic_px also counts the attach links out to the junction centres); chord_px; tortuosity
+    = arc_px / chord_px (None for a zero chord and for a closed chain); direction_deg in [0, 180) (None for a zero chord) (``polyline_stats``);
+    points, NumPy int32 [px, 2], y then x, in order (empty for a branch that is no chain); and with ``width_radius`` width_profile_px, fp64
+    [px], ``width_from_d2`` at the points.  The points of a unit travel in one tensor, one more read per unit; the chain flags travel with
+    the branch rows.  With ``save_dir``, crack_polylines.csv (``write_crack_polylines``) is written when the generator is exhausted; no
+    other file gains a column.  False (the default) adds nothing: no key, no file, no launch."""
     if topology is not True and topology is not False:
         raise ValueError(f"topology is True or False, got {topology!r}")
     if topology and measure_threshold is None:
@@ -838,6 +957,10 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         raise ValueError(f"branches is True or False, got {branches!r}")
     if branches and not topology:
         raise ValueError("branches are the segments of the topology's link graph: give topology=True (and measure_threshold) too")
+    if polylines is not True and polylines is not False:
+        raise ValueError(f"polylines is True or False, got {polylines!r}")
+    if polylines and not branches:
+        raise ValueError("polylines order the pixels of the branch table's segments: give branches=True (and topology, measure_threshold) too")
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
     min_px = None
     if min_crack_px is not None:
@@ -881,6 +1004,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
         extra, px, kept_labels, tables, wd2, whist, tmaps, bmaps, btables = [], None, [], None, [], [], [], [], []
+        rmaps, ptables = [], []
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
@@ -911,6 +1035,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                         bmaps.append(bl.view(H, W))
                         btables.append(branch_table(bl, topo, jl, None, d2))
                         btables[-1][:, 0] = j
+                        if polylines:
+                            _order_into(bl, topo, d2, rmaps, btables, ptables)
                     continue
                 labels = label_components(plane, measure)
                 acc = _component_sums(labels, sk)
@@ -940,6 +1066,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     bmaps.append(bl.view(H, W))
                     btables.append(branch_table(bl, topo, jl, kept, d2))
                     btables[-1][:, 0] = j
+                    if polylines:
+                        _order_into(bl, topo, d2, rmaps, btables, ptables)
                 table[:, 0] = j                              # the image within the unit
                 tables.append(table)
                 kept_labels.append(kept.view(H, W))
@@ -947,6 +1075,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             tables = torch.cat(tables).cpu().numpy() if min_px is not None else None         # and the unit's tables in one more
             whist = torch.stack(whist).cpu().numpy() if radius is not None else None         # the unit's histograms (and widest keys) in one
             btables = torch.cat(btables).cpu().numpy() if branches else None                 # the unit's branch rows in one more
+            ptables = torch.cat(ptables).cpu().numpy() if polylines else None                # and the unit's ordered points in one more
+            p_at = 0
             extra = [skel_u8]
         if saver is not None:
             planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
@@ -993,6 +1123,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     topologies.append((loader.names[i], tp))
                 if branches:
                     rows = btables[btables[:, 0] == j]
+                    if polylines:                            # the chain flag stands behind the table's columns
+                        rows, chain = rows[:, :-1], rows[:, -1]
                     of_label = {c["y"] * W + c["x"] + 1: k for k, c in enumerate(item["cracks"])} if min_px is not None else None
                     blist = crack_branches(rows, W, of_label)
                     kinds = [b["kind"] for b in blist]
@@ -1003,6 +1135,11 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                         per_crack = np.bincount([b["crack"] for b in blist], minlength=len(item["cracks"])).tolist()
                         for c, n in zip(item["cracks"], per_crack):
                             c["n_branches"] = n
+                    if polylines:
+                        npts = int(rows[chain != 0, 3].sum())                        # px of the chains: the image's span of the unit's points
+                        crack_polylines(blist, chain, ptables[p_at:p_at + npts], widths=radius is not None)
+                        p_at += npts
+                        item.update(n_chains=int((chain != 0).sum()), unordered_branch_px=int(rows[chain == 0, 3].sum()), rank_map=rmaps[j])
                     branch_rows.append((loader.names[i], blist))
             yield item
     if saver is not None:
@@ -1021,6 +1158,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                 write_crack_instance_topology(os.path.join(save_dir, "crack_instance_topology.csv"), instances)
         if branches:
             write_crack_branches(os.path.join(save_dir, "crack_branches.csv"), branch_rows)
+        if polylines:
+            write_crack_polylines(os.path.join(save_dir, "crack_polylines.csv"), branch_rows)
         if spur is not None:
             write_crack_spurs(os.path.join(save_dir, "crack_spurs.csv"), spurs)
             if min_px is not None:

@@ -3,6 +3,8 @@ model/utils/estimate_metrics.py:64-191 and model/engine/inference.py:50-53,111-1
 (csbsr_psnr_ssim, csbsr_iou_sweep) instead of five depthwise convolutions per SSIM and a [B,99,H,W] broadcast + a host numpy
 reduction per batch.  Same class names / call conventions as the reference; results come back as numpy arrays like there."""
 
+import math
+
 import numpy as np
 import torch
 
@@ -697,6 +699,114 @@ def summarize_branches(rows):
     out.update(longest_branch_px=float(length[-1]) if n else 0.0, median_branch_px=float(length[(n - 1) // 2]) if n else 0.0,
                total_branch_px=float(length.sum()) if n else 0.0)
     return out
+
+
+# ------------------------------------------------------------------------------------------- crack polylines
+ORDER_COLUMNS = ("y", "x", "diag", "d2")                     # a row of ``branch_polylines``' points
+PL_MAX_P = 1 << 28                                           # csrc/polylines.hip: the branch pixels one call orders
+
+
+def order_branches(blabels, topo, return_rounds=False):
+    """The position of every branch pixel along its branch (csrc/polylines.hip): (rank, diag), int32 device tensors [N, H, W],
+    for ``label_branches``' labels and ``skeleton_topology``'s topo.  The degree of a branch pixel is the number of its inner links; a
+    branch is a chain when no pixel of it has a degree above 2.  A chain with terminals (degree <= 1) starts at the terminal with the
+    smaller linear index y W + x; a chain without one (a cycle) starts at its first pixel in raster order and is walked from there first to
+    the start's neighbour with the smaller linear index.  rank = the inner links walked from the start (0 .. px - 1), diag = the SE / SW
+    links among them; both are -1 at clear pixels, at junction pixels and at every pixel of a branch that is no chain (a branch through a
+    full 2 x 2 quad).  The device ranks the compact list of the call's P branch pixels by pointer jumping in R = ceil(log2(P)) launches,
+    whatever the branches' lengths; the host reads P (8 bytes) once to size the list.  ``return_rounds`` = True adds R as a third result."""
+    if not (torch.is_tensor(blabels) and blabels.is_cuda and blabels.dtype == torch.int32 and blabels.dim() == 3):
+        raise ValueError("blabels is the int32 device tensor [N, H, W] of label_branches")
+    lib = L.load()
+    blabels = blabels.contiguous()
+    N, H, W = blabels.shape
+    dev = blabels.device
+    if not (torch.is_tensor(topo) and topo.dtype == torch.uint8 and tuple(topo.shape) == (N, H, W)):
+        raise ValueError("topo is the uint8 tensor [N, H, W] of skeleton_topology, one value per branch label")
+    topo = topo.to(dev).contiguous()
+    rank, diag = (torch.empty(N, H, W, dtype=torch.int32, device=dev) for _ in range(2))
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = L.stream(dev)
+        L.call("csbsr_branch_count", _ptr(topo), N, H, W, _ptr(count), st)
+        P = int(count.item())                                # the one read: it sizes the list and the rounds
+        need = int(lib.csbsr_branch_order_work_bytes(P)) if P <= PL_MAX_P else 0
+        if need <= 0:
+            raise L.CsbsrHipError(f"order_branches: {P} branch pixels are more than one call orders ({PL_MAX_P})")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call("csbsr_branch_order", _ptr(topo), _ptr(blabels), N, H, W, P, _ptr(work), _ptr(rank), _ptr(diag), st)
+    return (rank, diag, int(lib.csbsr_branch_order_rounds(P))) if return_rounds else (rank, diag)
+
+
+def branch_polylines(blabels, rank, diag, d2=None):
+    """The ordered points of every branch: (chain, offsets, points) -- bool [M], int64 [M + 1] and int32 [P_chain, 4] device tensors -- for
+    ``label_branches``' labels and ``order_branches``' rank and diag.  The M rows are those of ``branch_table``, in its order; row j's
+    points are points[offsets[j]:offsets[j + 1]], ``ORDER_COLUMNS`` = (y, x, diag, d2) per pixel from the branch's start to its stop, d2
+    from ``d2`` (``skeleton_width``'s) or 0.  chain[j] is False for a branch that ``order_branches`` left unordered; its span is empty.  No
+    sort: the device writes every pixel to row offsets[j] + rank."""
+    if not (torch.is_tensor(blabels) and blabels.is_cuda and blabels.dtype == torch.int32 and blabels.dim() == 3):
+        raise ValueError("blabels is the int32 device tensor [N, H, W] of label_branches")
+    L.load()
+    blabels = blabels.contiguous()
+    N, H, W = blabels.shape
+    dev = blabels.device
+    rank, diag = _plane_like(rank, blabels, "rank"), _plane_like(diag, blabels, "diag")
+    d2 = None if d2 is None else _plane_like(d2, blabels, "d2")
+    hw = H * W
+    flat, rk = blabels.view(N, hw), rank.view(-1)
+    roots = torch.nonzero(flat == torch.arange(1, hw + 1, dtype=torch.int32, device=dev))
+    root_g = roots[:, 0] * hw + roots[:, 1]                  # ascending: the order of branch_table
+    chain = rk[root_g] >= 0
+    at = torch.nonzero(rk >= 0).view(-1)                     # the ordered pixels
+    if at.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{at.numel()} ordered pixels do not fit the int32 rows of one table")
+    key = torch.div(at, hw, rounding_mode="floor") * hw + blabels.view(-1)[at].to(torch.int64) - 1
+    px = torch.bincount(torch.searchsorted(root_g, key), minlength=root_g.numel())[:root_g.numel()]
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(px * chain, 0)])
+    first = torch.empty(N * hw, dtype=torch.int32, device=dev)       # only the slots of root pixels hold values
+    first[root_g] = offsets[:-1].to(torch.int32)
+    points = torch.empty(at.numel(), 4, dtype=torch.int32, device=dev)
+    if at.numel() == 0:
+        return chain, offsets, points
+    with torch.cuda.device(dev):
+        L.call("csbsr_branch_scatter", _ptr(blabels), _ptr(rank), _ptr(diag), None if d2 is None else _ptr(d2), _ptr(first), N, H, W,
+               int(at.numel()), _ptr(points), L.stream(dev))
+    return chain, offsets, points
+
+
+def arc_position(rank, diag):
+    """the chain-code distance from the branch's start, fp64 on the host: (rank - diag) + sqrt(2) diag (ints, NumPy arrays or tensors; a
+    Python float for scalars).  It shares the bias of ``geodesic_length``."""
+    r, d = _host_ints(rank).astype(np.float64), _host_ints(diag).astype(np.float64)
+    s = (r - d) + _SQRT2 * d
+    return float(s) if s.ndim == 0 else s
+
+
+def _diag_along(points):
+    """int64 [px]: the diagonal steps up to each point of one branch's (y, x) rows"""
+    p = _host_ints(points).astype(np.int64)
+    if p.ndim != 2 or p.shape[1] < 2:
+        raise ValueError(f"points are [px, 2 or more] integers, y and x first, got shape {p.shape}")
+    step = np.diff(p[:, :2], axis=0)
+    return np.concatenate([np.zeros(min(1, p.shape[0]), np.int64), np.cumsum((step[:, 0] != 0) & (step[:, 1] != 0))])
+
+
+def polyline_stats(points, cycle=False):
+    """The figures of one branch's ordered points [px, 2 or more] (y and x first: a span of ``branch_polylines``' points), fp64 on the host:
+    start and stop, (y, x) tuples; arc_px, the chain-code length of the px - 1 inner links between them (``arc_position`` of the last
+    point); chord_px, the distance from start to stop; tortuosity = arc_px / chord_px, None when the chord is 0 or the branch is a cycle
+    (``cycle`` = True: the points do not tell -- the two ends of a path can be neighbours without a link); direction_deg, atan2(dy, dx) of
+    stop - start folded to [0, 180), None with a zero chord.  No point: start and stop are None, the lengths 0.0."""
+    p = _host_ints(points).astype(np.int64)
+    if p.size == 0:
+        return {"start": None, "stop": None, "arc_px": 0.0, "chord_px": 0.0, "tortuosity": None, "direction_deg": None}
+    nd = int(_diag_along(p)[-1])
+    arc = arc_position(p.shape[0] - 1, nd)
+    dy, dx = int(p[-1, 0] - p[0, 0]), int(p[-1, 1] - p[0, 1])
+    chord = math.sqrt(float(dy * dy + dx * dx))
+    return {"start": (int(p[0, 0]), int(p[0, 1])), "stop": (int(p[-1, 0]), int(p[-1, 1])), "arc_px": arc, "chord_px": chord,
+            "tortuosity": None if chord == 0 or cycle else arc / chord,
+            "direction_deg": None if chord == 0 else math.degrees(math.atan2(dy, dx)) % 180.0}
 
 
 class IoU:

@@ -759,6 +759,35 @@ int csbsr_branch_label(const uint8_t* topo, int32_t N, int32_t H, int32_t W, int
 int csbsr_branch_sums(const int32_t* blabels, const uint8_t* topo, const int32_t* jlabels, const int32_t* d2, int32_t N, int32_t H, int32_t W,
                       int32_t* bacc, csbsr_stream_t s);
 
+/* Crack polylines: the position of every branch pixel along its branch, and the ordered points of every branch (csrc/polylines.hip,
+ * DESIGN 1.16).  ``topo`` and ``blabels`` are those of csbsr_branch_label.  The degree of a branch pixel is the number of its inner links,
+ * owned or not.  A branch is a chain when no pixel of it has a degree above 2; a chain with terminals (degree <= 1) starts at the terminal with
+ * the smaller linear index, a chain without one (a cycle) at its first pixel blabel - 1, and is walked from there first to the start's
+ * neighbour with the smaller linear index.
+ *   csbsr_branch_count            : count int64 [1], zeroed by the entry on the stream = P, the branch pixels of all N planes.  The caller reads
+ *                                   it (the one host read of the chain) to size ``work``.
+ *   csbsr_branch_order_work_bytes : the bytes of ``work`` for P branch pixels (0 for a P the entry refuses).
+ *   csbsr_branch_order_rounds     : R = ceil(log2(P)) (0 for P <= 1), the pointer-jumping launches of csbsr_branch_order.
+ *   csbsr_branch_order            : rank and diag int32 [N][H][W], written at EVERY pixel: the inner links walked from the branch's start to
+ *                                   the pixel and the SE / SW links among them; -1 at clear pixels, at junction pixels and at every pixel of
+ *                                   a branch that is no chain.  P is csbsr_branch_count's value; work is 16-byte aligned scratch of
+ *                                   csbsr_branch_order_work_bytes(P) bytes, zeroed where needed by the entry.  R + 4 launches, none of them
+ *                                   proportional to a branch's length.  With a P below the true count some branch pixels are left out (wrong
+ *                                   numbers, no access outside an array).
+ *   csbsr_branch_scatter          : offsets int32 [N][H W], read ONLY at root pixels i = blabel - 1 of chains: the first row of the branch.
+ *                                   d2 int32 [N][H][W] or NULL.  points int32 [rows][4], 16-byte aligned: every pixel with rank >= 0 writes
+ *                                   (y, x, diag, d2 or 0) to row offsets[root] + rank; a row outside 0 .. rows - 1 is not written.
+ * 1 <= H, W <= 8192, 1 <= N <= 65535, 0 <= P <= 2^28; a null required pointer, an output that is also an input or another output, or a size
+ * outside these is refused (non-zero return) before anything is launched.  Integer arithmetic and integer atomics only: the slot order of
+ * the compact list differs from run to run, the results do not.  No entry synchronises with the host. */
+int csbsr_branch_count(const uint8_t* topo, int32_t N, int32_t H, int32_t W, int64_t* count, csbsr_stream_t s);
+int64_t csbsr_branch_order_work_bytes(int32_t P);
+int32_t csbsr_branch_order_rounds(int32_t P);
+int csbsr_branch_order(const uint8_t* topo, const int32_t* blabels, int32_t N, int32_t H, int32_t W, int32_t P, void* work, int32_t* rank,
+                       int32_t* diag, csbsr_stream_t s);
+int csbsr_branch_scatter(const int32_t* blabels, const int32_t* rank, const int32_t* diag, const int32_t* d2, const int32_t* offsets, int32_t N,
+                         int32_t H, int32_t W, int32_t rows, int32_t* points, csbsr_stream_t s);
+
 /* Spur pruning: the side branches of up to ``spur_px`` pixels of a binary plane go, the rest stays (csrc/prune.hip).  A pixel of
  * ``skeleton`` is set where its byte is non-zero; everything outside the plane -- another plane of the batch too -- is clear.  With the ring,
  * n8 and A of the topology entries, a set pixel is a tip iff A == 1 and n8 <= 3, and isolated iff n8 == 0.  Peel: X_0 = the plane; for
