@@ -197,6 +197,10 @@ SIGNATURES = {
     "csbsr_branch_order_rounds": (i32, [i32]),
     "csbsr_branch_order": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "csbsr_branch_scatter": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "csbsr_simplify_max_tol_q": (i32, []),
+    "csbsr_simplify_route_limits": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "csbsr_polyline_simplify_work_bytes": (i64, [i32, i32]),
+    "csbsr_polyline_simplify": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "csbsr_prune_max_spur": (i32, []),
     "csbsr_prune_steps": (i32, [C.POINTER(i32), C.POINTER(i32)]),
     "csbsr_prune_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),

@@ -12,9 +12,10 @@ connected crack (csrc/components.hip), (``width_radius``) with the local width a
 (``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip), and (``prune_spur_px``) with the
 centerline's short side branches removed before any of that is measured (csrc/prune.hip), and (``branches``) with one row per centerline
 segment between junctions (csrc/branches.hip), and (``polylines``) with every segment's pixels in order from end to end
-(csrc/polylines.hip)."""
+(csrc/polylines.hip), and (``simplify_px``) with those polylines simplified to their vertices (csrc/simplify.hip)."""
 import csv
 import gc
+import json
 import math
 import os
 
@@ -34,6 +35,7 @@ from .utils.estimate_metrics import _junction_labels, _count_roots, _component_t
 from .utils.estimate_metrics import prune_spurs, spur_length
 from .utils.estimate_metrics import label_branches, branch_table, branch_kinds, BRANCH_COLUMNS, BRANCH_KINDS, _SQRT2
 from .utils.estimate_metrics import order_branches, branch_polylines, arc_position, _diag_along
+from .utils.estimate_metrics import simplify_tolerance, simplify_polylines, polyline_length
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -665,6 +667,130 @@ def read_crack_polylines(path):
     return out
 
 
+VERTEX_CSV_COLUMNS = ["name", "branch", "i", "index", "y", "x"]
+VERTEX_CSV_OPTIONAL = ["width_px"]                          # behind the others, only where the branches carry vertex_width_px
+
+
+def _closed_chain(b):
+    """a chain with as many inner links as pixels: the rule of ``crack_polylines``"""
+    return bool(b["chain"]) and sum(b["links"]) - b["attach"] == b["px"]
+
+
+def crack_vertices(branches, points, keep, widths=False):
+    """adds the keys of ``predict_dataset(simplify_px=)`` to the dicts of one image's ``branches`` list, which carry the polyline keys:
+    ``points`` int [P_chain, 4] is the table ``crack_polylines`` took and ``keep`` [P_chain] of 0 / 1 the host copy of
+    ``simplify_polylines``' flags for its rows.  New keys: vertices (NumPy int32 [v, 2], y then x: the kept points in order; empty for a
+    branch that is no chain), vertex_index (int32 [v], their positions in ``points``), length_simplified_px (``polyline_length`` of the
+    vertices, closed where the chain is -- a chain with as many inner links as pixels --, None for a branch that is no chain) and with
+    ``widths`` vertex_width_px (fp64 [v], ``width_from_d2`` of the d2 column).  Returns (the image's vertices, the sum of the lengths).
+    All branches at once: one pass over the image's rows, no arithmetic per branch but for the closed chains."""
+    points = np.asarray(points, np.int64).reshape(-1, 4)
+    keep = np.asarray(keep).reshape(-1) != 0
+    n = np.array([b["points"].shape[0] for b in branches], np.int64)
+    off = np.concatenate([np.zeros(1, np.int64), np.cumsum(n)])
+    if off[-1] != points.shape[0] or keep.shape[0] != points.shape[0]:
+        raise ValueError(f"{points.shape[0]} points and {keep.shape[0]} flags for chains of {int(off[-1])} pixels")
+    rows = np.nonzero(keep)[0]
+    voff = np.concatenate([np.zeros(1, np.int64), np.cumsum(keep)])[off]             # the first vertex of every branch
+    vc = np.diff(voff)
+    verts = points[rows, :2].astype(np.int32)
+    index = (rows - np.repeat(off[:-1], vc)).astype(np.int32)
+    step = np.diff(verts.astype(np.float64), axis=0)
+    seg = np.concatenate([np.sqrt(step[:, 0] * step[:, 0] + step[:, 1] * step[:, 1]), np.zeros(2)])      # seg[k]: from vertex k to k + 1
+    ends = np.stack([voff[:-1], np.maximum(voff[1:] - 1, voff[:-1])], 1).reshape(-1)
+    length = np.where(vc >= 2, np.add.reduceat(seg, ends)[::2], 0.0) if len(branches) else np.zeros(0)
+    width = np.atleast_1d(width_from_d2(points[rows, 3])).astype(np.float64) if widths else None
+    total = 0.0
+    for b, v0, v1, s in zip(branches, voff[:-1].tolist(), voff[1:].tolist(), length.tolist()):
+        b["vertices"], b["vertex_index"] = verts[v0:v1], index[v0:v1]
+        if not b["chain"]:
+            b["length_simplified_px"] = None
+        else:
+            b["length_simplified_px"] = polyline_length(verts[v0:v1], closed=True) if _closed_chain(b) else s
+            total += b["length_simplified_px"]
+        if widths:
+            b["vertex_width_px"] = width[v0:v1]
+    return int(rows.size), total
+
+
+def write_crack_vertices(path, rows):
+    """crack_vertices.csv: one row per vertex -- ``rows`` = (name, the image's ``branches`` list with the vertex keys) per image; ``branch``
+    is the numbering of crack_branches.csv, i the vertex's position along the simplified polyline, index its position in the branch's
+    ``points`` (the i of crack_polylines.csv), width_px (with ``width_radius``) its local width.  A branch that is no chain has no row."""
+    first = next((b[0] for _, b in rows if b), {})
+    wide = "vertex_width_px" in first
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(VERTEX_CSV_COLUMNS + (VERTEX_CSV_OPTIONAL if wide else []))
+        for name, branches in rows:
+            for j, b in enumerate(branches):
+                for i, ((y, x), k) in enumerate(zip(np.asarray(b["vertices"]).reshape(-1, 2).tolist(), np.asarray(b["vertex_index"]).tolist())):
+                    w.writerow([name, j, i, k, y, x] + ([repr(float(b["vertex_width_px"][i]))] if wide else []))
+
+
+def read_crack_vertices(path):
+    """what ``write_crack_vertices`` wrote: (name, [dict(branch, vertices int32 [v, 2], vertex_index int32 [v] and, where the file has it,
+    width_px fp64 [v])]) per image that has a vertex, the branches in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    n = len(VERTEX_CSV_COLUMNS)
+    if rows[0][:n] != VERTEX_CSV_COLUMNS or rows[0][n:] not in ([], VERTEX_CSV_OPTIONAL):
+        raise ValueError(f"{path}: not a crack_vertices.csv header: {rows[0]}")
+    wide = len(rows[0]) > n
+    out = []
+    for r in rows[1:]:
+        if not out or out[-1][0] != r[0]:
+            out.append((r[0], []))
+        if not out[-1][1] or out[-1][1][-1]["branch"] != int(r[1]):
+            if out[-1][1] and out[-1][1][-1]["branch"] > int(r[1]):
+                raise ValueError(f"{path}: branch {r[1]} of {r[0]} is out of order")
+            out[-1][1].append(dict(branch=int(r[1]), vertices=[], vertex_index=[], **({"width_px": []} if wide else {})))
+        d = out[-1][1][-1]
+        if int(r[2]) != len(d["vertices"]):
+            raise ValueError(f"{path}: vertex {r[2]} of branch {r[1]} of {r[0]} is out of order")
+        d["vertex_index"].append(int(r[3]))
+        d["vertices"].append((int(r[4]), int(r[5])))
+        if wide:
+            d["width_px"].append(float(r[6]))
+    for _, branches in out:
+        for d in branches:
+            d["vertices"] = np.array(d["vertices"], np.int32).reshape(-1, 2)
+            d["vertex_index"] = np.array(d["vertex_index"], np.int32)
+            if wide:
+                d["width_px"] = np.array(d["width_px"], np.float64)
+    return out
+
+
+def crack_geojson(rows):
+    """the FeatureCollection of crack_polylines.geojson as a dict: one Feature per chain of ``rows`` = (name, the image's ``branches`` list
+    with the vertex keys) per image.  The geometry is a LineString of [x, y] in pixels -- a closed chain repeats its first vertex -- or, for
+    a chain of one vertex, a Point; the properties are name, branch (the numbering of crack_branches.csv), kind, closed, px, n_vertices,
+    arc_px, length_simplified_px and, where the dicts have them, crack, max_width_px and min_width_px."""
+    features = []
+    for name, branches in rows:
+        for j, b in enumerate(branches):
+            if not b["chain"]:
+                continue
+            xy = [[int(x), int(y)] for y, x in np.asarray(b["vertices"]).reshape(-1, 2).tolist()]
+            closed = _closed_chain(b)
+            if len(xy) == 1:
+                geometry = {"type": "Point", "coordinates": xy[0]}
+            else:
+                geometry = {"type": "LineString", "coordinates": xy + (xy[:1] if closed else [])}
+            prop = dict(name=name, branch=j, kind=b["kind"], closed=closed, px=int(b["px"]), n_vertices=len(xy), arc_px=float(b["arc_px"]),
+                        length_simplified_px=float(b["length_simplified_px"]))
+            prop.update({k: int(b[k]) if k == "crack" else float(b[k]) for k in ("crack", "max_width_px", "min_width_px") if k in b})
+            features.append({"type": "Feature", "geometry": geometry, "properties": prop})
+    return {"type": "FeatureCollection", "features": features}
+
+
+def write_crack_geojson(path, rows):
+    """crack_polylines.geojson: ``crack_geojson`` of ``rows`` with sorted keys, so that two runs give the same bytes"""
+    with open(path, "w") as fh:
+        fh.write(json.dumps(crack_geojson(rows), sort_keys=True))
+        fh.write("\n")
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -846,11 +972,14 @@ def _topology_ints(sk):
     return topo, ints, jl
 
 
-def _order_into(bl, topo, d2, rmaps, btables, ptables):
-    """the polylines of one image's branch labels: its rank map, the chain flag behind the image's branch rows, its ordered points"""
+def _order_into(bl, topo, d2, rmaps, btables, ptables, simplify_px=None, ktables=None):
+    """the polylines of one image's branch labels: its rank map, the chain flag behind the image's branch rows, its ordered points and,
+    with ``simplify_px``, the kept flag of every point"""
     H, W = bl.shape[-2:]
     rank, diag = order_branches(bl, topo)
-    chain, _, points = branch_polylines(bl, rank, diag, d2)
+    chain, offsets, points = branch_polylines(bl, rank, diag, d2)
+    if simplify_px is not None:
+        ktables.append(simplify_polylines(offsets, points, simplify_px)[0])
     rmaps.append(rank.view(H, W))
     btables[-1] = torch.cat([btables[-1], chain.to(torch.int32).view(-1, 1)], 1)
     ptables.append(points)
@@ -858,7 +987,7 @@ def _order_into(bl, topo, d2, rmaps, btables, ptables):
 
 @torch.no_grad()
 def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
-                    width_radius=None, topology=False, prune_spur_px=None, branches=False, polylines=False):
+                    width_radius=None, topology=False, prune_spur_px=None, branches=False, polylines=False, simplify_px=None):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -948,7 +1077,19 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     points, NumPy int32 [px, 2], y then x, in order (empty for a branch that is no chain); and with ``width_radius`` width_profile_px, fp64
     [px], ``width_from_d2`` at the points.  The points of a unit travel in one tensor, one more read per unit; the chain flags travel with
     the branch rows.  With ``save_dir``, crack_polylines.csv (``write_crack_polylines``) is written when the generator is exhausted; no
-    other file gains a column.  False (the default) adds nothing: no key, no file, no launch."""
+    other file gains a column.  False (the default) adds nothing: no key, no file, no launch.
+
+    ``simplify_px`` = T, a multiple of 0.25 in [0, 16] (``simplify_tolerance``; it needs ``polylines`` = True; anything else is a ValueError
+    before the model runs), simplifies the polylines the call reports -- kept with ``min_crack_px``, pruned with ``prune_spur_px`` -- by
+    Douglas-Peucker with the tolerance T in pixels (``simplify_polylines``): a point stays where dropping it would move the line
+    by more than T.  New keys: n_vertices (int) and length_simplified_px (the sum over the chains).  Every dict of ``branches`` gains
+    vertices, NumPy int32 [v, 2], y then x (empty for a branch that is no chain); vertex_index, int32 [v], their positions in points;
+    length_simplified_px, the Euclidean length of the simplified polyline (``polyline_length``; with the closing segment for a closed
+    chain, None for a branch that is no chain) -- exact on a digital straight line once T exceeds the rounding of the line's ends, 1 px at
+    the most, where arc_px reads up to 8.24 % long --; and with
+    ``width_radius`` vertex_width_px, fp64 [v].  The kept flags of a unit travel in one tensor, one more read per unit.  With ``save_dir``,
+    crack_vertices.csv (``write_crack_vertices``) and crack_polylines.geojson (``write_crack_geojson``) are written when the generator is
+    exhausted; no other file gains a column.  None (the default) adds nothing: no key, no file, no launch."""
     if topology is not True and topology is not False:
         raise ValueError(f"topology is True or False, got {topology!r}")
     if topology and measure_threshold is None:
@@ -961,6 +1102,10 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         raise ValueError(f"polylines is True or False, got {polylines!r}")
     if polylines and not branches:
         raise ValueError("polylines order the pixels of the branch table's segments: give branches=True (and topology, measure_threshold) too")
+    if simplify_px is not None:
+        if not polylines:
+            raise ValueError("simplify_px simplifies the polylines: give polylines=True (and branches, topology, measure_threshold) too")
+        simplify_tolerance(simplify_px, "simplify_px")
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
     min_px = None
     if min_crack_px is not None:
@@ -1004,7 +1149,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         layout = [(int(loader.pix_offsets[i]), int(loader.out_dims[i, 0]), int(loader.out_dims[i, 1]),
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
         extra, px, kept_labels, tables, wd2, whist, tmaps, bmaps, btables = [], None, [], None, [], [], [], [], []
-        rmaps, ptables = [], []
+        rmaps, ptables, ktables = [], [], []
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
@@ -1036,7 +1181,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                         btables.append(branch_table(bl, topo, jl, None, d2))
                         btables[-1][:, 0] = j
                         if polylines:
-                            _order_into(bl, topo, d2, rmaps, btables, ptables)
+                            _order_into(bl, topo, d2, rmaps, btables, ptables, simplify_px, ktables)
                     continue
                 labels = label_components(plane, measure)
                 acc = _component_sums(labels, sk)
@@ -1067,7 +1212,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     btables.append(branch_table(bl, topo, jl, kept, d2))
                     btables[-1][:, 0] = j
                     if polylines:
-                        _order_into(bl, topo, d2, rmaps, btables, ptables)
+                        _order_into(bl, topo, d2, rmaps, btables, ptables, simplify_px, ktables)
                 table[:, 0] = j                              # the image within the unit
                 tables.append(table)
                 kept_labels.append(kept.view(H, W))
@@ -1076,6 +1221,7 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             whist = torch.stack(whist).cpu().numpy() if radius is not None else None         # the unit's histograms (and widest keys) in one
             btables = torch.cat(btables).cpu().numpy() if branches else None                 # the unit's branch rows in one more
             ptables = torch.cat(ptables).cpu().numpy() if polylines else None                # and the unit's ordered points in one more
+            ktables = torch.cat(ktables).cpu().numpy() if simplify_px is not None else None  # and their kept flags in one more
             p_at = 0
             extra = [skel_u8]
         if saver is not None:
@@ -1138,6 +1284,9 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     if polylines:
                         npts = int(rows[chain != 0, 3].sum())                        # px of the chains: the image's span of the unit's points
                         crack_polylines(blist, chain, ptables[p_at:p_at + npts], widths=radius is not None)
+                        if simplify_px is not None:
+                            nv, total = crack_vertices(blist, ptables[p_at:p_at + npts], ktables[p_at:p_at + npts], widths=radius is not None)
+                            item.update(n_vertices=nv, length_simplified_px=total)
                         p_at += npts
                         item.update(n_chains=int((chain != 0).sum()), unordered_branch_px=int(rows[chain == 0, 3].sum()), rank_map=rmaps[j])
                     branch_rows.append((loader.names[i], blist))
@@ -1160,6 +1309,9 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             write_crack_branches(os.path.join(save_dir, "crack_branches.csv"), branch_rows)
         if polylines:
             write_crack_polylines(os.path.join(save_dir, "crack_polylines.csv"), branch_rows)
+        if simplify_px is not None:
+            write_crack_vertices(os.path.join(save_dir, "crack_vertices.csv"), branch_rows)
+            write_crack_geojson(os.path.join(save_dir, "crack_polylines.geojson"), branch_rows)
         if spur is not None:
             write_crack_spurs(os.path.join(save_dir, "crack_spurs.csv"), spurs)
             if min_px is not None:

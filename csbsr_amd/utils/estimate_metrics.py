@@ -809,6 +809,69 @@ def polyline_stats(points, cycle=False):
             "direction_deg": None if chord == 0 else math.degrees(math.atan2(dy, dx)) % 180.0}
 
 
+# ------------------------------------------------------------------------------------------- simplified polylines
+SIMPLIFY_MAX_PX = 16.0                                       # csrc/simplify.hip: SP_MAX_TOL_Q quarter pixels
+SIMPLIFY_ROUTE_LIMITS = (64, 2048)                           # csrc/simplify.hip: SP_WAVE_MAX, SP_LDS_MAX -- the longest span of a wave, of LDS
+
+
+def simplify_tolerance(px, what="tolerance_px"):
+    """the tolerance in quarter pixels: ``px`` is an int or a float (Python or NumPy, not a bool) that is an exact multiple of 0.25 in
+    [0, 16]; anything else is a ValueError"""
+    ok = not isinstance(px, (bool, np.bool_)) and isinstance(px, (int, float, np.integer, np.floating))
+    if ok:
+        q = float(px) * 4.0                                  # exact: a power of two
+        ok = math.isfinite(q) and q == math.floor(q) and 0.0 <= q <= 4.0 * SIMPLIFY_MAX_PX
+    if not ok:
+        raise ValueError(f"{what} is a multiple of 0.25 in [0, {SIMPLIFY_MAX_PX:g}], got {px!r}")
+    return int(q)
+
+
+def simplify_polylines(offsets, points, tolerance_px):
+    """Douglas-Peucker on every span of ``branch_polylines``' table (csrc/simplify.hip): (keep, voffsets, vindex) -- uint8 [P],
+    int64 [M + 1] and int32 [V] device tensors -- for offsets int64 [M + 1] and points int32 [P, 4] (only y and x are read) on the device.
+    keep is 1 at the rows that stay; vindex holds those rows ascending, so the vertices are points[vindex], and span j's are
+    vindex[voffsets[j]:voffsets[j + 1]].  The first and the last row of a span always stay; an inner row stays iff it is the farthest from
+    the segment between its kept neighbours (the smallest row among equals) and farther than ``tolerance_px`` (``simplify_tolerance``),
+    compared in integers.  A closed chain is the open polyline from its first to its last row.  Nothing is read by the host."""
+    tol_q = simplify_tolerance(tolerance_px)
+    if not (torch.is_tensor(offsets) and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 1):
+        raise ValueError("offsets is the int64 device tensor [M + 1] of branch_polylines")
+    if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.int32 and points.dim() == 2 and points.shape[1] == 4
+            and points.device == offsets.device):
+        raise ValueError("points is the int32 device tensor [P, 4] of branch_polylines, on the device of offsets")
+    lib = L.load()
+    dev = offsets.device
+    offsets, points = offsets.contiguous(), points.contiguous()
+    M, P = offsets.numel() - 1, points.shape[0]
+    if M == 0 or P == 0:
+        return torch.zeros(P, dtype=torch.uint8, device=dev), torch.zeros(M + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+    need = int(lib.csbsr_polyline_simplify_work_bytes(M, P)) if M <= PL_MAX_P and P <= PL_MAX_P else 0
+    if need <= 0:
+        raise L.CsbsrHipError(f"simplify_polylines: {M} spans over {P} rows are more than one call takes ({PL_MAX_P})")
+    keep = torch.empty(P, dtype=torch.uint8, device=dev)     # the entry writes every row
+    vcount = torch.empty(M, dtype=torch.int32, device=dev)
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.call("csbsr_polyline_simplify", _ptr(offsets), _ptr(points), M, P, tol_q, _ptr(work), _ptr(keep), _ptr(vcount), L.stream(dev))
+    voffsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(vcount, 0, dtype=torch.int64)])
+    return keep, voffsets, torch.nonzero(keep).view(-1).to(torch.int32)
+
+
+def polyline_length(yx, closed=False):
+    """the Euclidean length of the polyline through the vertices ``yx`` [v, 2 or more] (y and x first), fp64 on the host: the sum of its
+    segments' lengths, with ``closed`` also the segment from the last vertex back to the first; 0.0 for fewer than two vertices"""
+    p = _host_ints(yx).astype(np.float64)
+    if p.ndim != 2 or p.shape[1] < 2:
+        raise ValueError(f"yx is [v, 2 or more], y and x first, got shape {p.shape}")
+    p = p[:, :2]
+    if p.shape[0] < 2:
+        return 0.0
+    if closed:
+        p = np.concatenate([p, p[:1]])
+    d = np.diff(p, axis=0)
+    return float(np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).sum())
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

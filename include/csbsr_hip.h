@@ -788,6 +788,36 @@ int csbsr_branch_order(const uint8_t* topo, const int32_t* blabels, int32_t N, i
 int csbsr_branch_scatter(const int32_t* blabels, const int32_t* rank, const int32_t* diag, const int32_t* d2, const int32_t* offsets, int32_t N,
                          int32_t H, int32_t W, int32_t rows, int32_t* points, csbsr_stream_t s);
 
+/* Polyline simplification (Douglas-Peucker) of the ordered points of every branch (csrc/simplify.hip).  offsets int64 [M + 1]
+ * and points int32 [P][4], 16-byte aligned, are the table of csbsr_branch_scatter's caller: span j is rows offsets[j] .. offsets[j + 1] - 1,
+ * and only y and x (columns 0 and 1) are read.  tol_q is the tolerance in quarter pixels.  For a segment from kept point a to kept point b
+ * and a point p strictly between them along the chain, c2 = |b - a|^2, t = (p - a).(b - a), and the key (int64) is |p - a|^2 if c2 = 0,
+ * |p - a|^2 c2 if t <= 0, |p - b|^2 c2 if t >= c2, else cross(b - a, p - a)^2: the squared distance to the segment, times c2.  The candidate
+ * of a segment is the inner point with the largest key, among equal keys the one with the smallest row; it is kept iff
+ * 16 key > tol_q^2 c2 (with c2 = 0: 16 key > tol_q^2).  A kept point splits the segment, and both halves are treated the same way.  The first
+ * and the last row of a span are always kept; a span of 0, 1 or 2 rows keeps what it has.  A closed chain gets no special rule: it is the open
+ * polyline from its first to its last row.  With coordinates in [0, 8192) every term stays below 2^58; coordinates outside give unspecified
+ * flags and no access outside an array.
+ *   csbsr_simplify_max_tol_q           : 64 (16 px).
+ *   csbsr_simplify_route_limits        : the longest span a wave owns (its state in registers) and the longest chain whose state a workgroup
+ *                                        keeps in LDS; a longer one keeps it in ``work``.  The flags do not depend on the route.
+ *   csbsr_polyline_simplify_work_bytes : the bytes of ``work`` for M spans over P rows (0 for arguments the entry refuses).
+ *   csbsr_polyline_simplify            : keep uint8 [P], written at EVERY row: 1 where the row stays, 0 where it goes and at rows that no span
+ *                                        covers.  vcount int32 [M]: the rows kept per span.  work: 16-byte aligned scratch, touched only at the
+ *                                        rows of chains longer than the LDS limit.  A span whose offsets descend or leave 0 .. P is skipped
+ *                                        (vcount 0): wrong numbers, no access outside an array.  One memset and two launches; the rounds of a
+ *                                        chain run inside the kernel until one splits nothing -- at most one round per row, each a pass
+ *                                        over the chain: up to n^2 / 256 steps a lane for a chain of n rows (a saw whose teeth grow).  The
+ *                                        caller bounds the length of a chain; the chains of an image have at most H W rows.
+ * 0 <= M <= 2^28, 0 <= P <= 2^28, 0 <= tol_q <= 64; a null pointer, an output that is an input, the other output or work, a work or points
+ * that is not 16-byte aligned, or a value outside these is refused (non-zero return) before anything is launched.  Integer arithmetic only:
+ * results are run-to-run identical.  Nothing is read back by the host. */
+int32_t csbsr_simplify_max_tol_q(void);
+int csbsr_simplify_route_limits(int32_t* wave_max, int32_t* lds_max);
+int64_t csbsr_polyline_simplify_work_bytes(int32_t M, int32_t P);
+int csbsr_polyline_simplify(const int64_t* offsets, const int32_t* points, int32_t M, int32_t P, int32_t tol_q, void* work, uint8_t* keep,
+                            int32_t* vcount, csbsr_stream_t s);
+
 /* Spur pruning: the side branches of up to ``spur_px`` pixels of a binary plane go, the rest stays (csrc/prune.hip).  A pixel of
  * ``skeleton`` is set where its byte is non-zero; everything outside the plane -- another plane of the batch too -- is clear.  With the ring,
  * n8 and A of the topology entries, a set pixel is a tip iff A == 1 and n8 <= 3, and isolated iff n8 == 0.  Peel: X_0 = the plane; for
