@@ -201,6 +201,10 @@ SIGNATURES = {
     "csbsr_simplify_route_limits": (i32, [C.POINTER(i32), C.POINTER(i32)]),
     "csbsr_polyline_simplify_work_bytes": (i64, [i32, i32]),
     "csbsr_polyline_simplify": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "csbsr_gap_max_radius": (i32, []),
+    "csbsr_endpoint_gaps": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "csbsr_gap_groups": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "csbsr_gap_draw": (i32, [vp, i32, i32, i32, vp, vp]),
     "csbsr_prune_max_spur": (i32, []),
     "csbsr_prune_steps": (i32, [C.POINTER(i32), C.POINTER(i32)]),
     "csbsr_prune_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),

@@ -12,7 +12,8 @@ connected crack (csrc/components.hip), (``width_radius``) with the local width a
 (``topology``) with the ends, junctions, loops and geodesic length of the centerline (csrc/topology.hip), and (``prune_spur_px``) with the
 centerline's short side branches removed before any of that is measured (csrc/prune.hip), and (``branches``) with one row per centerline
 segment between junctions (csrc/branches.hip), and (``polylines``) with every segment's pixels in order from end to end
-(csrc/polylines.hip), and (``simplify_px``) with those polylines simplified to their vertices (csrc/simplify.hip)."""
+(csrc/polylines.hip), and (``simplify_px``) with those polylines simplified to their vertices (csrc/simplify.hip), and (``bridge_gap_px``)
+with the gaps between the ends of one crack and the nearest other crack, the cracks they join and the bridges drawn (csrc/gaps.hip)."""
 import csv
 import gc
 import json
@@ -36,6 +37,8 @@ from .utils.estimate_metrics import prune_spurs, spur_length
 from .utils.estimate_metrics import label_branches, branch_table, branch_kinds, BRANCH_COLUMNS, BRANCH_KINDS, _SQRT2
 from .utils.estimate_metrics import order_branches, branch_polylines, arc_position, _diag_along
 from .utils.estimate_metrics import simplify_tolerance, simplify_polylines, polyline_length
+from .utils.estimate_metrics import gap_radius, gap_target, endpoint_gaps, gap_table, gap_groups, draw_bridges, gap_length, gap_group_of
+from .utils.estimate_metrics import summarize_gaps, GAP_COLUMNS, TOPO_ISOLATED, TOPO_END
 
 THRESHOLDS = [i * 0.01 for i in range(1, 100)]           # inference.py:50
 
@@ -791,6 +794,66 @@ def write_crack_geojson(path, rows):
         fh.write("\n")
 
 
+GAP_CSV_COLUMNS = ["name", "gap", "y", "x", "to_y", "to_x", "gap_px", "d2", "kind", "mutual"]
+GAP_CSV_OPTIONAL = ["crack", "to_crack"]                    # behind the others, where the gaps carry them (``min_crack_px``)
+GAP_KINDS = ("end_end", "end_side")
+
+
+def crack_gaps(rows, W, crack_of_label=None):
+    """the ``gaps`` list of ``predict_dataset`` from the host rows of ``gap_table`` (``GAP_COLUMNS``) of one image: dict(y, x, to, gap_px, d2,
+    kind, mutual) per gap, in raster order of the source (y, x); ``to`` = (y, x) of the target, kind "end_end" where the target is an end
+    or an isolated pixel, else "end_side".  ``crack_of_label`` (component label -> index into ``cracks``) adds crack and to_crack."""
+    c = {k: j for j, k in enumerate(GAP_COLUMNS)}
+    rows = np.asarray(rows, np.int64).reshape(-1, len(GAP_COLUMNS))
+    py, px = np.divmod(rows[:, c["p"]], W)
+    qy, qx = np.divmod(rows[:, c["q"]], W)
+    ends = (rows[:, c["class_q"]] == TOPO_ISOLATED) | (rows[:, c["class_q"]] == TOPO_END)
+    length = np.asarray(gap_length(rows[:, c["d2"]]), np.float64).reshape(-1)
+    out = [dict(y=y, x=x, to=(ty, tx), gap_px=g, d2=d2, kind=GAP_KINDS[0] if e else GAP_KINDS[1], mutual=bool(m))
+           for y, x, ty, tx, g, d2, e, m in zip(py.tolist(), px.tolist(), qy.tolist(), qx.tolist(), length.tolist(), rows[:, c["d2"]].tolist(),
+                                                ends.tolist(), rows[:, c["mutual"]].tolist())]
+    if crack_of_label is not None:
+        for d, (a, b) in zip(out, rows[:, [c["label_p"], c["label_q"]]].tolist()):
+            d.update(crack=crack_of_label[a], to_crack=crack_of_label[b])
+    return out
+
+
+def write_crack_gaps(path, rows):
+    """crack_gaps.csv: one row per gap -- ``rows`` = (name, the image's ``gaps`` list) per image; ``gap`` numbers an image's gaps in raster
+    order of their source, ``crack`` / ``to_crack`` (with ``min_crack_px``) are the numbering of crack_instances.csv"""
+    first = next((g[0] for _, g in rows if g), {})
+    optional = [k for k in GAP_CSV_OPTIONAL if k in first]
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(GAP_CSV_COLUMNS + optional)
+        for name, gaps in rows:
+            for j, g in enumerate(gaps):
+                w.writerow([name, j, int(g["y"]), int(g["x"]), int(g["to"][0]), int(g["to"][1]), repr(float(g["gap_px"])), int(g["d2"]), g["kind"],
+                            int(bool(g["mutual"]))] + [int(g[k]) for k in optional])
+
+
+def read_crack_gaps(path):
+    """what ``write_crack_gaps`` wrote: (name, [dict]) per image that has a gap, in the file's order"""
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    n = len(GAP_CSV_COLUMNS)
+    optional = rows[0][n:]
+    if rows[0][:n] != GAP_CSV_COLUMNS or optional not in ([], GAP_CSV_OPTIONAL):
+        raise ValueError(f"{path}: not a crack_gaps.csv header: {rows[0]}")
+    out = []
+    for r in rows[1:]:
+        if not out or out[-1][0] != r[0]:
+            out.append((r[0], []))
+        if int(r[1]) != len(out[-1][1]):
+            raise ValueError(f"{path}: gap {r[1]} of {r[0]} is out of order")
+        if r[8] not in GAP_KINDS or r[9] not in ("0", "1"):
+            raise ValueError(f"{path}: {r[8]!r}, {r[9]!r} is no gap kind and mutual flag")
+        d = dict(y=int(r[2]), x=int(r[3]), to=(int(r[4]), int(r[5])), gap_px=float(r[6]), d2=int(r[7]), kind=r[8], mutual=r[9] == "1")
+        d.update({k: int(v) for k, v in zip(optional, r[n:])})
+        out[-1][1].append(d)
+    return out
+
+
 class _Saver:
     """The files ``test.py --sf_save_image`` writes (model/utils/save_output.py), fed with uint8 buffers through a ring of pinned slots:
     ``push`` enqueues non-blocking copies on the current stream and records the slot's event, ``drain`` waits on that event alone and
@@ -799,12 +862,12 @@ class _Saver:
     A batch is (img [B,H,W,3], raw [B,H,W,1], planes [B,S,H,W], kern [B * nP,1,K,K]) of equal images, or, with ``layout`` = one
     (pixel offset, H, W, first kernel, kernels) per image, flat pools of images of any size: img [3 * npix] interleaved per image, raw [npix],
     planes [1,S,npix], kern [sum of kernels,1,K,K].  With ``skeletons`` a fifth tensor follows, skel [npix] of 0 / 255 laid out like raw, and
-    goes to skeletons/<name>."""
+    goes to skeletons/<name>; with ``bridged`` a sixth of the same kind, which goes to skeletons_bridged/<name>."""
 
-    def __init__(self, save_dir, thresholds, skeletons=False):
+    def __init__(self, save_dir, thresholds, skeletons=False, bridged=False):
         self.dir = save_dir
         self.th_names = [f"th_{thresholds[i]:.2f}" for i in SAVE_THRESHOLD_IDX if i < len(thresholds)] + ["th_-1.00"]
-        for d in ["images", "kernels", "kernels_origin"] + [os.path.join("masks", t) for t in self.th_names] + ["skeletons"] * bool(skeletons):
+        for d in ["images", "kernels", "kernels_origin"] + [os.path.join("masks", t) for t in self.th_names] + ["skeletons"] * bool(skeletons) + ["skeletons_bridged"] * bool(bridged):
             os.makedirs(os.path.join(save_dir, d), exist_ok=True)
         self.ring, self.n, self.pending = [None] * _SLOTS, 0, []
 
@@ -834,6 +897,7 @@ class _Saver:
             ev.synchronize()                                 # this slot's copies only
             img, raw, planes = img.numpy(), raw.numpy(), planes.numpy()
             skel = views[4].numpy() if len(views) > 4 else None
+            bridged = views[5].numpy() if len(views) > 5 else None
             nP = kern.shape[0] // len(fnames)
             for b, name in enumerate(fnames):
                 if layout is None:
@@ -849,6 +913,9 @@ class _Saver:
                 if skel is not None:
                     o, H, W = layout[b][:3]
                     Image.fromarray(skel[o:o + H * W].reshape(H, W)).save(os.path.join(self.dir, "skeletons", name))
+                if bridged is not None:
+                    o, H, W = layout[b][:3]
+                    Image.fromarray(bridged[o:o + H * W].reshape(H, W)).save(os.path.join(self.dir, "skeletons_bridged", name))
                 stem = name.replace(".png", "")
                 for j in range(nP):                          # save_kernel: 441 values per patch, on the host
                     k = kern[k0 + j]
@@ -985,9 +1052,35 @@ def _order_into(bl, topo, d2, rmaps, btables, ptables, simplify_px=None, ktables
     ptables.append(points)
 
 
+def _bridge_into(j, topo, lab, sk, gap, to, px, gtables, gmaps, glabels, bridged_u8, count_cracks):
+    """the gaps of one image: its gap rows, bridge map, group labels and bridged skeleton (0 / 255), and two integers in front of the
+    topology's twelve in the image's row of the unit's read -- bridge_px = |bridges & ~skeleton| and, with ``count_cracks``, the labels that
+    have a skeleton pixel (else 0)"""
+    _, H, W = topo.shape
+    lab = lab.view(1, H, W)
+    gq, gd2 = endpoint_gaps(topo, lab, gap, to)
+    rows = gap_table(topo, lab, gq, gd2)
+    rows[:, 0] = j                                           # the image within the unit
+    gtables.append(rows)
+    bm = draw_bridges(gq).view(-1)
+    gmaps.append(bm.view(H, W))
+    glabels.append(gap_groups(lab, gq).view(H, W))
+    bridged_u8.copy_((sk | bm) * 255)
+    if count_cracks:
+        seen = torch.zeros(H * W + 1, dtype=torch.bool, device=lab.device)
+        seen[(lab.view(-1) * (sk != 0)).long()] = True
+        n_seen = seen[1:].sum()
+    else:
+        n_seen = torch.zeros((), dtype=torch.int64, device=lab.device)
+    ints = torch.stack([(bm * (sk == 0)).sum(), n_seen])
+    k = TOPO_COUNTS + 2
+    px[-1] = torch.cat([px[-1][:-k], ints, px[-1][-k:]])
+
+
 @torch.no_grad()
 def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=None, measure_threshold=None, min_crack_px=None,
-                    width_radius=None, topology=False, prune_spur_px=None, branches=False, polylines=False, simplify_px=None):
+                    width_radius=None, topology=False, prune_spur_px=None, branches=False, polylines=False, simplify_px=None, bridge_gap_px=None,
+                    bridge_to="any"):
     """``inference_tti_building`` (model/engine/inference.py:210-273) over a ``DevicePredictLoader``: LR images only, every window through
     ``model`` (any callable with JointModel's evaluation signature), and the owned part of every output patch into its image by
     csbsr_stitch_tiles_u8 -- the SR image clipped, as bytes; the map unclipped, as fp32 and as bytes.  Unlike the reference's unfold, every
@@ -1089,7 +1182,31 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
     the most, where arc_px reads up to 8.24 % long --; and with
     ``width_radius`` vertex_width_px, fp64 [v].  The kept flags of a unit travel in one tensor, one more read per unit.  With ``save_dir``,
     crack_vertices.csv (``write_crack_vertices``) and crack_polylines.geojson (``write_crack_geojson``) are written when the generator is
-    exhausted; no other file gains a column.  None (the default) adds nothing: no key, no file, no launch."""
+    exhausted; no other file gains a column.  None (the default) adds nothing: no key, no file, no launch.
+
+    ``bridge_gap_px`` = G, a whole number 2 .. 64 (``gap_radius``; it needs ``measure_threshold`` and ``topology`` = True), with ``bridge_to``
+    = "any" (the default) or "end" (anything else, or a ``bridge_to`` other than "any" without ``bridge_gap_px``, is a ValueError before the
+    model runs), says which of the cracks the call reports are one crack (``endpoint_gaps``): a map thresholded at one level
+    breaks a thin crack wherever it dips below the threshold.  For every end and isolated pixel of the skeleton the call reports -- pruned
+    with ``prune_spur_px``, kept with ``min_crack_px`` -- it finds the nearest centerline pixel of ANOTHER crack within G pixels ("end": the
+    nearest end or isolated pixel), the first in raster order among equals: the end's gap.  The cracks are those of ``cracks``: the labels
+    are the kept labels with ``min_crack_px``, else ``label_components`` of the stitched map at ``measure_threshold``.  New keys: n_gaps;
+    n_mutual_gaps (the gaps whose target's gap leads back: a mutual pair is two of them); gap_length_px (the sum of the gaps' lengths, a
+    mutual pair counted once) and max_gap_px (``summarize_gaps``); bridge_px, the pixels of the bridges -- the 8-connected Bresenham line
+    of every gap, ``draw_bridges`` -- that are no skeleton pixels; n_cracks_bridged, the number of groups when the cracks a gap joins count
+    as one: with ``min_crack_px`` n_cracks minus the joins, the groups among the dicts of ``cracks``; without it the components of R that
+    have a pixel on the reported skeleton (the number to compare it with) minus the joins; gaps, a list in raster order of the source of
+    dict(y, x, to=(y, x), gap_px, d2, kind, mutual) -- kind "end_end" where the target is an end or an isolated pixel, else "end_side"
+    (``crack_gaps``) --, with ``min_crack_px`` each also with crack and to_crack, indices into ``cracks``; bridge_map (device uint8 [H, W],
+    0 / 1) and bridged_labels (device int32 [H, W]: every pixel of a crack carries the smallest label of its group, ``gap_groups``).  With
+    ``min_crack_px`` every dict of ``cracks`` gains group, the index into ``cracks`` of its group's first crack, and gaps, the number of gaps
+    that start in it.  The bridged skeleton is NOT re-measured: topology, branches, polylines and widths describe the unbridged one.  There
+    is no direction test: an end bridges to the nearest other crack even when that crack runs beside it -- ``bridge_to`` = "end" and kind /
+    mutual are the filters offered.  A fragment below ``min_crack_px`` is removed before the bridging and cannot be rescued by it, and a
+    bridge may run over pixels of the end's own crack.  The unit's integers stay in its one read; the gap rows travel in a tensor of
+    their own, one more read per unit.  With ``save_dir``, skeletons_bridged/<name> (0 / 255, skeleton | bridges) goes through the ring and
+    crack_gaps.csv (``write_crack_gaps``) is written when the generator is exhausted; no other file gains a column.  None (the default)
+    adds nothing: no key, no file, no launch."""
     if topology is not True and topology is not False:
         raise ValueError(f"topology is True or False, got {topology!r}")
     if topology and measure_threshold is None:
@@ -1106,6 +1223,14 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         if not polylines:
             raise ValueError("simplify_px simplifies the polylines: give polylines=True (and branches, topology, measure_threshold) too")
         simplify_tolerance(simplify_px, "simplify_px")
+    gap = None
+    gap_target(bridge_to, "bridge_to")
+    if bridge_gap_px is not None:
+        if measure_threshold is None or not topology:
+            raise ValueError("bridge_gap_px bridges the ends of the topology: give topology=True and measure_threshold too")
+        gap = gap_radius(bridge_gap_px, "bridge_gap_px")
+    elif bridge_to != "any":
+        raise ValueError(f"bridge_to={bridge_to!r} says where bridge_gap_px may bridge to: give bridge_gap_px too")
     measure = None if measure_threshold is None else unit_threshold(measure_threshold, "measure_threshold")
     min_px = None
     if min_crack_px is not None:
@@ -1124,8 +1249,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         spur = spur_length(prune_spur_px, "prune_spur_px")
     saver = None
     if save_dir is not None:
-        saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True)
-    stats, instances, widths, topologies, spurs, branch_rows = [], [], [], [], [], []
+        saver = _Saver(save_dir, thresholds) if measure is None else _Saver(save_dir, thresholds, skeletons=True, bridged=gap is not None)
+    stats, instances, widths, topologies, spurs, branch_rows, gap_rows = [], [], [], [], [], [], []
     th32 = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
     save_th = th32[[i for i in SAVE_THRESHOLD_IDX if i < len(thresholds)]].to(loader.device) if saver is not None else None
     s, dev = loader.scale, loader.device
@@ -1150,8 +1275,10 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                    int(loader.tile_start[i]) - unit.t0, int(loader.tile_start[i + 1] - loader.tile_start[i])) for i in range(unit.i0, unit.i1)]
         extra, px, kept_labels, tables, wd2, whist, tmaps, bmaps, btables = [], None, [], None, [], [], [], [], []
         rmaps, ptables, ktables = [], [], []
+        gtables, gmaps, glabels = [], [], []
         if measure is not None:
             skel_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev)
+            bridged_u8 = torch.empty(unit.npix, dtype=torch.uint8, device=dev) if gap is not None else None
             t32 = torch.tensor(measure, dtype=torch.float32, device=dev)
             px, tables = [], []
             for j, (o, H, W, _, _) in enumerate(layout):     # one plane per image: the stitched map, never a tile
@@ -1170,6 +1297,9 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                         topo, tints, jl = _topology_ints(sk.view(1, H, W))
                         tmaps.append(topo.view(H, W))
                         px[-1] = torch.cat([px[-1], tints])
+                    if gap is not None:                      # the cracks are the components of R
+                        lab = label_components(plane, measure)
+                        _bridge_into(j, topo, lab, sk, gap, bridge_to, px, gtables, gmaps, glabels, bridged_u8[o:o + H * W], True)
                     d2 = None
                     if radius is not None:
                         d2, hist = skeleton_width(plane, sk.view(1, H, W), measure, radius)
@@ -1206,6 +1336,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     tmaps.append(topo.view(H, W))
                     px[-1] = torch.cat([px[-1], tints])
                     table = torch.cat([table, _topology_columns(table, _component_topology(labels, topo, jl))], 1)
+                if gap is not None:                          # the cracks are the kept components
+                    _bridge_into(j, topo, kept, sk, gap, bridge_to, px, gtables, gmaps, glabels, bridged_u8[o:o + H * W], False)
                 if branches:                                 # a tensor of their own: the topology columns stay the table's last
                     bl = label_branches(topo)
                     bmaps.append(bl.view(H, W))
@@ -1222,8 +1354,9 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
             btables = torch.cat(btables).cpu().numpy() if branches else None                 # the unit's branch rows in one more
             ptables = torch.cat(ptables).cpu().numpy() if polylines else None                # and the unit's ordered points in one more
             ktables = torch.cat(ktables).cpu().numpy() if simplify_px is not None else None  # and their kept flags in one more
+            gtables = torch.cat(gtables).cpu().numpy() if gap is not None else None          # the unit's gap rows in one more
             p_at = 0
-            extra = [skel_u8]
+            extra = [skel_u8] + ([bridged_u8] if gap is not None else [])
         if saver is not None:
             planes = threshold_planes_u8(map_f32.view(1, -1), save_th)
             saver.push(loader.names[unit.i0:unit.i1], [sr_u8, map_u8, planes, kernels] + extra, layout=layout)
@@ -1267,6 +1400,21 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
                     tp["mean_width_geodesic_px"] = mean_width_geodesic(crack, tp["length_geodesic_px"])
                     item.update(tp, topology_map=tmaps[j])
                     topologies.append((loader.names[i], tp))
+                if gap is not None:
+                    rows = gtables[gtables[:, 0] == j]
+                    bridge_px, n_with_skeleton = (int(v) for v in px[j][-TOPO_COUNTS - 4:-TOPO_COUNTS - 2])     # in front of the topology's twelve
+                    of_label = {c["y"] * W + c["x"] + 1: k for k, c in enumerate(item["cracks"])} if min_px is not None else None
+                    gs = summarize_gaps(rows, item["n_cracks"] if min_px is not None else n_with_skeleton)
+                    glist = crack_gaps(rows, W, of_label)
+                    item.update(n_gaps=gs["n_gaps"], n_mutual_gaps=gs["n_mutual"], gap_length_px=gs["gap_length_px"], max_gap_px=gs["max_gap_px"],
+                                bridge_px=bridge_px, n_cracks_bridged=gs["n_cracks_bridged"], gaps=glist, bridge_map=gmaps[j], bridged_labels=glabels[j])
+                    if min_px is not None:
+                        group = gap_group_of(rows)
+                        starts = np.bincount([g["crack"] for g in glist], minlength=len(item["cracks"])).tolist()
+                        for c, n in zip(item["cracks"], starts):
+                            lab = c["y"] * W + c["x"] + 1
+                            c.update(group=of_label[group.get(lab, lab)], gaps=n)
+                    gap_rows.append((loader.names[i], glist))
                 if branches:
                     rows = btables[btables[:, 0] == j]
                     if polylines:                            # the chain flag stands behind the table's columns
@@ -1312,6 +1460,8 @@ def predict_dataset(model, loader, *, ksize=21, thresholds=THRESHOLDS, save_dir=
         if simplify_px is not None:
             write_crack_vertices(os.path.join(save_dir, "crack_vertices.csv"), branch_rows)
             write_crack_geojson(os.path.join(save_dir, "crack_polylines.geojson"), branch_rows)
+        if gap is not None:
+            write_crack_gaps(os.path.join(save_dir, "crack_gaps.csv"), gap_rows)
         if spur is not None:
             write_crack_spurs(os.path.join(save_dir, "crack_spurs.csv"), spurs)
             if min_px is not None:

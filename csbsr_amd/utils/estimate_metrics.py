@@ -872,6 +872,149 @@ def polyline_length(yx, closed=False):
     return float(np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).sum())
 
 
+# ------------------------------------------------------------------------------------------- crack gap bridging
+GAP_MAX_RADIUS = 64                                          # csrc/gaps.hip: csbsr_gap_max_radius()
+GAP_COLUMNS = ("plane", "p", "q", "d2", "label_p", "label_q", "class_q", "mutual")
+GAP_TO = ("any", "end")
+
+
+def gap_radius(G, what="max_gap"):
+    """the largest gap that is bridged, in pixels: a whole number 2 .. 64 (Python or NumPy, not a bool), anything else is a ValueError.  Two
+    different 8-connected components are never closer than d2 = 4, so 1 could never find anything and is refused."""
+    if isinstance(G, (bool, np.bool_)) or not isinstance(G, (int, np.integer)) or not 2 <= G <= GAP_MAX_RADIUS:
+        raise ValueError(f"{what} is a whole number 2 .. {GAP_MAX_RADIUS}, got {G!r}")
+    return int(G)
+
+
+def gap_target(to, what="to"):
+    """what an end may bridge to: "any" centerline pixel of another crack, or only an "end" (an end or an isolated pixel)"""
+    if not isinstance(to, str) or to not in GAP_TO:
+        raise ValueError(f'{what} is "any" or "end", got {to!r}')
+    return to
+
+
+def _gap_planes(topo, labels):
+    labels = _labels(labels)                                 # a host tensor is refused before anything is moved
+    topo = _topo(topo)
+    if tuple(labels.shape) != tuple(topo.shape) or labels.device != topo.device:
+        raise ValueError(f"labels {tuple(labels.shape)} has one value per topo byte {tuple(topo.shape)}, on the same device")
+    return topo, labels
+
+
+def _gap_map(t, like, what):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and (like is None or tuple(t.shape) == tuple(like.shape))):
+        raise ValueError(f"{what} is the int32 device tensor [N, H, W] of endpoint_gaps")
+    return t.contiguous()
+
+
+def endpoint_gaps(topo, labels, max_gap, to="any"):
+    """For every end of the centerline the nearest centerline pixel of another crack (csrc/gaps.hip): (gap_q, gap_d2), int32
+    device tensors [N, H, W], for ``skeleton_topology``'s topo and an int32 device label map [N, H, W] (``label_components``', or any other:
+    two pixels belong to the same crack iff their labels are equal and non-zero).  A source is a pixel of class end or isolated with a
+    label; a candidate for it a pixel q of the same plane with a class (``to`` = "end": an end or an isolated pixel), a label other than
+    the source's and d2 = |q - p|^2 <= ``max_gap``^2 (``gap_radius``).  gap_q is the linear index y W + x of the candidate with the smallest
+    (d2, q) -- the nearest, among equals the first in raster order -- and gap_d2 its d2; -1 and 0 at every other pixel.  Planes are
+    independent and nothing is read by the host."""
+    G, to = gap_radius(max_gap), gap_target(to)
+    topo, labels = _gap_planes(topo, labels)
+    L.load()
+    N, H, W = topo.shape
+    gap_q, gap_d2 = (torch.empty(N, H, W, dtype=torch.int32, device=topo.device) for _ in range(2))
+    with torch.cuda.device(topo.device):
+        L.call("csbsr_endpoint_gaps", _ptr(topo), _ptr(labels), N, H, W, G, int(to == "end"), _ptr(gap_q), _ptr(gap_d2), L.stream(topo.device))
+    return gap_q, gap_d2
+
+
+def gap_table(topo, labels, gap_q, gap_d2):
+    """One row per gap of ``endpoint_gaps``: int32 device tensor [M, 8] = ``GAP_COLUMNS``, in raster order of the source p, plane by plane.
+    p and q are linear indices within the plane, label_p / label_q ``labels`` there, class_q the class of the target (1 isolated, 2 end,
+    3 path, 4 junction) and mutual 1 where the gap of q is p.  Built with indexing on the device; nothing is read by the host."""
+    topo, labels = _gap_planes(topo, labels)
+    gap_q, gap_d2 = _gap_map(gap_q, labels, "gap_q"), _gap_map(gap_d2, labels, "gap_d2")
+    N, H, W = labels.shape
+    fq = gap_q.view(N, H * W)
+    at = torch.nonzero(fq >= 0)
+    n, p = at[:, 0], at[:, 1]
+    q = fq[n, p].long()
+    fl = labels.view(N, H * W)
+    cols = [n, p, q, gap_d2.view(N, H * W)[n, p], fl[n, p], fl[n, q], topo.view(N, H * W)[n, q] & 7, fq[n, q] == p]
+    return torch.stack([c.to(torch.int64) for c in cols], 1).to(torch.int32)
+
+
+def gap_groups(labels, gap_q):
+    """The cracks joined by the gaps: int32 device tensor [N, H, W], 0 where ``labels`` is 0, else the smallest label of the pixel's group --
+    the labels connected by the transitive closure of "a gap leads from a pixel of label a to a pixel of label b" (csbsr_gap_groups: the
+    lock-free union-find of the component labelling over the labels).  With ``label_components``' labels (1 + the first pixel's linear
+    index) that is the group's first pixel in raster order.  The labels lie in 1 .. H W.  Nothing is read by the host."""
+    labels = _labels(labels)
+    gap_q = _gap_map(gap_q, labels, "gap_q")
+    L.load()
+    N, H, W = labels.shape
+    parent, groups = (torch.empty(N, H, W, dtype=torch.int32, device=labels.device) for _ in range(2))
+    with torch.cuda.device(labels.device):
+        L.call("csbsr_gap_groups", _ptr(labels), _ptr(gap_q), N, H, W, _ptr(parent), _ptr(groups), L.stream(labels.device))
+    return groups
+
+
+def draw_bridges(gap_q):
+    """The bridges of the gaps: uint8 device tensor [N, H, W] of 0 / 1 with the 8-connected Bresenham line of every gap (p, gap_q[p]), drawn
+    from the end with the smaller linear index, both ends included (csbsr_gap_draw).  The bridged skeleton is skeleton | bridges."""
+    gap_q = _gap_map(gap_q, None, "gap_q")
+    L.load()
+    N, H, W = gap_q.shape
+    out = torch.empty(N, H, W, dtype=torch.uint8, device=gap_q.device)
+    with torch.cuda.device(gap_q.device):
+        L.call("csbsr_gap_draw", _ptr(gap_q), N, H, W, _ptr(out), L.stream(gap_q.device))
+    return out
+
+
+def gap_length(d2):
+    """the length of a gap in pixels, fp64 on the host: sqrt(d2) (ints, NumPy arrays or tensors; a Python float for a scalar)"""
+    g = np.sqrt(_host_ints(d2).astype(np.float64))
+    return float(g) if g.ndim == 0 else g
+
+
+def _gap_rows(rows):
+    rows = _host_ints(rows).astype(np.int64)
+    if rows.ndim != 2 or rows.shape[1] != len(GAP_COLUMNS):
+        if rows.size:
+            raise ValueError(f"rows is [M, {len(GAP_COLUMNS)}], the rows of gap_table, got shape {rows.shape}")
+        rows = rows.reshape(0, len(GAP_COLUMNS))
+    return rows
+
+
+def gap_group_of(rows):
+    """label -> the smallest label of its group, for the labels that the rows of ONE plane name (a union-find on the host)"""
+    parent = {}
+
+    def find(i):
+        while parent.setdefault(i, i) != i:
+            i = parent[i]
+        return i
+    for a, b in _gap_rows(rows)[:, 4:6].tolist():
+        a, b = find(a), find(b)
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+    return {k: find(k) for k in parent}
+
+
+def summarize_gaps(rows, n_cracks):
+    """The gap figures of ONE plane from its rows of ``gap_table``, fp64 on the host: n_gaps (the rows), n_mutual (the rows whose target's
+    gap leads back: a mutual pair is two of them), n_end_to_end (the target is an end or an isolated pixel), n_end_to_side (it is a path or
+    a junction pixel), gap_length_px (the sum of ``gap_length``, a mutual pair counted once), max_gap_px, and n_cracks_bridged = ``n_cracks``
+    minus the joins the gaps make: the groups among ``n_cracks`` cracks that include every label of the rows."""
+    rows = _gap_rows(rows)
+    if isinstance(n_cracks, (bool, np.bool_)) or not isinstance(n_cracks, (int, np.integer)) or n_cracks < 0:
+        raise ValueError(f"n_cracks is a whole number >= 0, got {n_cracks!r}")
+    once = (rows[:, 7] == 0) | (rows[:, 1] < rows[:, 2])
+    ee = int(((rows[:, 6] == TOPO_ISOLATED) | (rows[:, 6] == TOPO_END)).sum())
+    group = gap_group_of(rows)
+    return {"n_gaps": int(rows.shape[0]), "n_mutual": int((rows[:, 7] != 0).sum()), "n_end_to_end": ee, "n_end_to_side": int(rows.shape[0]) - ee,
+            "gap_length_px": float(np.sqrt(rows[once, 3].astype(np.float64)).sum()),
+            "max_gap_px": float(np.sqrt(np.float64(rows[:, 3].max()))) if rows.shape[0] else 0.0,
+            "n_cracks_bridged": int(n_cracks) - (len(group) - len(set(group.values())))}
+
+
 class IoU:
     """estimate_metrics.py:64-84 for binary maps (threshold 0.5)."""
     name = "IoU"

@@ -818,6 +818,35 @@ int64_t csbsr_polyline_simplify_work_bytes(int32_t M, int32_t P);
 int csbsr_polyline_simplify(const int64_t* offsets, const int32_t* points, int32_t M, int32_t P, int32_t tol_q, void* work, uint8_t* keep,
                             int32_t* vcount, csbsr_stream_t s);
 
+/* Crack gap bridging: for every end of the centerline the nearest centerline pixel of another crack within a gap of G pixels, the cracks
+ * such gaps join, and the bridges drawn (csrc/gaps.hip).  ``topo`` is csbsr_skeleton_topology's byte plane (class = bits 0-2:
+ * 0 clear, 1 isolated, 2 end, 3 path, 4 junction), ``labels`` any int32 label map: two pixels belong to the same crack iff their labels are
+ * equal and non-zero.  A source is a pixel p of class 1 or 2 with labels[p] != 0.  A candidate for p is a pixel q of the SAME plane with
+ * class != 0 (to_end = 1: class 1 or 2), labels[q] != 0, labels[q] != labels[p] and d2 = |q - p|^2 <= G^2.  The gap of p is the candidate
+ * with the smallest (d2, linear index y W + x of q): the nearest, and among equals the first in raster order.
+ *   csbsr_gap_max_radius : the largest G, 64.
+ *   csbsr_endpoint_gaps  : topo uint8 [N][H][W], labels int32 [N][H][W].  gap_q, gap_d2 int32 [N][H][W], written at EVERY pixel (the caller
+ *                          does not clear them): at a source that has a gap the linear index of its target within the plane and its d2,
+ *                          -1 and 0 at every other pixel.
+ *   csbsr_gap_groups     : labels with 1 <= label <= H W at every labelled pixel (csbsr_ccl_label's are), gap_q as above.  parent int32
+ *                          [N][H W] of scratch.  group_labels int32 [N][H][W], written at EVERY pixel: 0 where labels is 0, else the
+ *                          smallest label of the pixel's group -- the labels joined by the transitive closure of "a gap leads from a pixel
+ *                          of label a to a pixel of label b".  A minimum over a set: the bits do not depend on scheduling.  A label outside
+ *                          1 .. H W joins nothing and gets 0.  Three launches.
+ *   csbsr_gap_draw       : bridge_map uint8 [N][H][W], cleared by the entry on the stream, then 1 on the 8-connected Bresenham line of every
+ *                          gap, drawn from the end with the smaller linear index (y0, x0) to the other (y1, x1): dx = |x1 - x0|, dy = y1 -
+ *                          y0, sx = sign(x1 - x0), err = dx - dy; plot, stop at (y1, x1), e2 = 2 err, if e2 > -dy: err -= dy, x += sx; if
+ *                          e2 < dx: err += dx, y += 1.  Both ends are plotted.
+ * 1 <= H, W <= 8192, 1 <= N <= 65535, 2 <= G <= 64, to_end 0 or 1; a null pointer, an output that is another argument or a value outside
+ * these is refused (non-zero return) before anything is launched.  Integers only: results are run-to-run identical.  No entry synchronises
+ * with the host. */
+int32_t csbsr_gap_max_radius(void);
+int csbsr_endpoint_gaps(const uint8_t* topo, const int32_t* labels, int32_t N, int32_t H, int32_t W, int32_t G, int32_t to_end, int32_t* gap_q,
+                        int32_t* gap_d2, csbsr_stream_t s);
+int csbsr_gap_groups(const int32_t* labels, const int32_t* gap_q, int32_t N, int32_t H, int32_t W, int32_t* parent, int32_t* group_labels,
+                     csbsr_stream_t s);
+int csbsr_gap_draw(const int32_t* gap_q, int32_t N, int32_t H, int32_t W, uint8_t* bridge_map, csbsr_stream_t s);
+
 /* Spur pruning: the side branches of up to ``spur_px`` pixels of a binary plane go, the rest stays (csrc/prune.hip).  A pixel of
  * ``skeleton`` is set where its byte is non-zero; everything outside the plane -- another plane of the batch too -- is clear.  With the ring,
  * n8 and A of the topology entries, a set pixel is a tip iff A == 1 and n8 <= 3, and isolated iff n8 == 0.  Peel: X_0 = the plane; for
